@@ -19,6 +19,7 @@ is what the device alone sustains: the same pictures, command buffers built and 
 re-run every step.  `roofline` is about kernel device time (hipEvents on the decoder's stream inside the timed region).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]         N > 1: starts N ranks itself (one per GPU)
+    python bench.py ... --dump-outputs DIR                      + the last timed step's decoded pictures (sampled) as .npy
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -283,6 +284,31 @@ def cpu_baseline(gops, decs, W, H, BD, GOP, full=True, CF=1):
     return cpu, parity
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs: all files together stay under 64 MB
+DUMP_SEED = 0xDE265D
+
+
+def dump_outputs(out_dir, decs, W, H, BD, GOP):
+    """--dump-outputs DIR: what the timed path delivered in its last step - every stream's decoded pictures in its DPB, the
+    planes a caller of de265hip_dpb_download receives - as DIR/{y,cb,cr}.npy, float32 of shape (streams, GOP, n): row [s, k]
+    is picture k of stream s.  A 4K step holds far more than the budget, so every plane is reduced to a fixed sample of
+    positions (seeded: the same for every picture and every run; all positions where the step fits the budget)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cw, ch = decs[0]._chroma_dims(0, W, H)
+    sizes = [W * H, cw * ch, cw * ch]
+    frac = min(1.0, DUMP_BUDGET_BYTES / 4.0 / (len(decs) * GOP * sum(sizes)))
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = [np.sort(rng.choice(n, max(1, int(n * frac)), replace=False)) if frac < 1.0 else np.arange(n) for n in sizes]
+    out = [np.empty((len(decs), GOP, len(i)), np.float32) for i in idx]
+    for s_i, d in enumerate(decs):
+        for k in range(GOP):
+            for c, plane in enumerate(d.download(k, W, H, BD)):
+                out[c][s_i, k] = plane.ravel()[idx[c]]
+    for name, a in zip(("y", "cb", "cr"), out):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -329,7 +355,12 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher rehearsal without a GPU (tests/test_bench_launcher.py): ranks rendezvous over gloo, time an empty "
                          "region with the barrier + MAX-over-ranks timer, rank 0 prints the JSON line with value null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's decoded pictures of the last timed step to DIR/{y,cb,cr}.npy "
+                         "(float32, a fixed seeded sample of every plane; at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -523,6 +554,8 @@ def main():
     ktimes_replay = collect()           # the dominant kernel's launches of that region (all kernels' with --events all)
     for d in decs:
         d.set_profiling(False)
+    if args.dump_outputs and args.no_host_inclusive and rank == 0:     # (the replay is the timed path)
+        dump_outputs(args.dump_outputs, decs, W, H, BD, GOP)
     device_replay = {"value": round(world * args.steps * GOP * S / replay_elapsed, 2), "unit": "frames/s", "steps": args.steps,
                      "ms_per_step": round(1e3 * replay_elapsed / args.steps, 3),
                      "host_enqueue_ms_per_step": round(1e3 * t_host / args.steps, 3),
@@ -561,6 +594,8 @@ def main():
         ktimes = collect()
         for d in decs:
             d.set_profiling(False)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, decs, W, H, BD, GOP)
         # ---- (2b) the same product path with every decoded picture DELIVERED: copied out through de265hip_dpb_download_async
         # into pinned host planes inside the timed region (what de265_get_image_plane hands an application), PCIe included
         copy_out = None

@@ -1,15 +1,15 @@
 """Pins the oracle's constant tables: (a) against the closed forms / properties the
-HEVC design gives them, (b) against the table text in the reference sources when
-/root/reference is present (reading source text only -- nothing is compiled or run)."""
+HEVC design gives them, (b) against the table text in the reference sources, as
+tests/golden/ref_tables.json holds it (tools/ref_source_golden.py; where the sources are
+present, the file is checked against them too -- reading source text only, nothing is
+compiled or run)."""
 import os
 import re
 
 import numpy as np
-import pytest
 
 import pyoracle
-
-REF = "/root/reference/libde265"
+import ref_source_golden
 
 
 def oracle_dct():
@@ -52,27 +52,18 @@ def test_small_tables_known_values():
         assert inv[m - 11] == round(8192 / a)          # invAngle = round(8192 / intraPredAngle)
 
 
-def _ref_array(fname, decl_regex, count):
-    txt = open(os.path.join(REF, fname)).read()
-    m = re.search(decl_regex + r"[^=]*=\s*\{(.*?)\};", txt, re.S)
-    assert m, decl_regex
-    body = re.sub(r"//.*", "", m.group(1))
-    nums = [int(x) for x in re.findall(r"-?\d+", body)]
-    assert len(nums) == count, (decl_regex, len(nums))
-    return nums
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference sources not present (GPU box)")
 def test_tables_equal_reference_text():
-    assert list(oracle_dct().ravel()) == _ref_array("fallback-dct.cc", r"static int8_t mat_dct\[32\]\[32\]", 1024)
-    assert tab("dst", 16) == _ref_array("fallback-dct.cc", r"static int8_t mat_8_357\[4\]\[4\]", 16)
-    assert tab("beta", 52) == _ref_array("deblock.cc", r"static uint8_t table_8_23_beta\[52\]", 52)
-    assert tab("tc", 54) == _ref_array("deblock.cc", r"static uint8_t table_8_23_tc\[54\]", 54)
-    assert tab("angle", 35) == _ref_array("intrapred.cc", r"const int intraPredAngle_table\[1\+34\]", 35)
-    assert tab("invangle", 15) == _ref_array("intrapred.cc", r"static const int invAngle_table\[25-10\]", 15)
-    assert tab("lscale", 6) == _ref_array("transform.cc", r"static const int levelScale\[\]", 6)
-    assert [pyoracle.lib().oracle_table(b"qpc", q) for q in range(30, 44)][:14] == \
-        _ref_array("transform.cc", r"const int tab8_22\[\]", 14)
+    ref = ref_source_golden.stored_tables()
+    if ref_source_golden.have_sources():
+        assert ref_source_golden.tables_from_sources() == ref, "tests/golden/ref_tables.json is stale"
+    assert list(oracle_dct().ravel()) == ref["mat_dct"]
+    assert tab("dst", 16) == ref["mat_8_357"]
+    assert tab("beta", 52) == ref["table_8_23_beta"]
+    assert tab("tc", 54) == ref["table_8_23_tc"]
+    assert tab("angle", 35) == ref["intraPredAngle_table"]
+    assert tab("invangle", 15) == ref["invAngle_table"]
+    assert tab("lscale", 6) == ref["levelScale"]
+    assert [pyoracle.lib().oracle_table(b"qpc", q) for q in range(30, 44)][:14] == ref["tab8_22"]
 
 
 def test_device_tables_equal_oracle_tables():
