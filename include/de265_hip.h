@@ -348,6 +348,28 @@ int  de265hip_dpb_copy(de265hip_decoder* src_dec, int src_slot, de265hip_decoder
  * de265hip_picture_run() of the picture waits for the upload on the device. */
 int  de265hip_picture_build(de265hip_decoder*, int dst_slot,
                             const de265hip_picture_desc*, de265hip_picture** out);
+/* Structured builds: the device derives the deblocking edge bits.  A host that keeps libde265's CU / TU structure planes hands them
+ * over instead of running derive_edgeFlags (deblock.cc:31-237) or de265hip_derive_edge_flags itself.  The three planes are the
+ * ones de265hip_derive_edge_flags takes (image.h:67-68, 193-216):
+ *   - With a structure, the edge bits (DE265HIP_BLK_EDGE_*, 0xF0) of desc->blk_flags are IGNORED.  The device writes them before
+ *     any kernel of the picture reads them, bit-exact with derive_edgeFlags, and keeps the low nibble the host sent.
+ *   - Validation on the host (DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE): a NULL plane; log2_min_cb_size outside [3, log2_ctb_size];
+ *     a cb_log2_size entry outside {0} and [log2_min_cb_size, log2_ctb_size]; a part mode above 7.
+ *   - Any other inconsistent structure (a CB quadtree that does not tile the picture, split bits below MinTb) leaves the device
+ *     memory-safe and the picture decodes; its edge bits are then unspecified, and stay inside the picture.
+ *   - The planes are copied during the call, like the desc's arrays.
+ * For the recorder: de265hip_record_structure (below).  de265hip_pipeline_submit_desc stays unstructured. */
+typedef struct de265hip_cu_structure {
+  const uint8_t* cb_log2_size;        /* per MinCb unit, ceil(W/MinCb) x ceil(H/MinCb): log2 CB size at a CB's top-left unit, 0 elsewhere */
+  const uint8_t* cb_part_mode;        /* per MinCb unit: PartMode 0..7 at the top-left unit */
+  const uint8_t* tu_split;            /* per MinTb unit over whole CTBs ((PicWidthInCtbs << (log2_ctb - log2_min_tb)) wide): bit d =
+                                         split_transform_flag at depth d */
+} de265hip_cu_structure;
+int  de265hip_picture_build_structured(de265hip_decoder*, int dst_slot, const de265hip_picture_desc*,
+                                       const de265hip_cu_structure*, de265hip_picture** out);
+int  de265hip_picture_build_host_structured(de265hip_decoder*, int dst_slot, const de265hip_picture_desc*,
+                                            const de265hip_cu_structure*, de265hip_picture** out);
+
 /* Run: enqueue all reconstruction kernels of the picture on the decoder's
  * stream (asynchronous).  last_stage: DE265HIP_STAGE_*. */
 int  de265hip_picture_run(de265hip_decoder*, de265hip_picture*, int last_stage);
@@ -376,6 +398,11 @@ int  de265hip_record_ctb(de265hip_recorder*, int ctb_addr_rs, const de265hip_ctb
 /* metadata planes (ceil(W/4) x ceil(H/4)); copied */
 int  de265hip_record_blk_planes(de265hip_recorder*, const uint8_t* blk_flags, const int8_t* blk_qp_y,
                                 const de265hip_motion* blk_motion /* may be NULL */);
+/* the CU / TU structure planes (de265hip_cu_structure; copied): from now on de265hip_recorder_submit and the pipeline's `prepare`
+ * path build this recorder's picture STRUCTURED - the edge bits of the recorded blk_flags are ignored and derived on the device.
+ * This is how an integrated libde265 drops its derive_edgeFlags call. */
+int  de265hip_record_structure(de265hip_recorder*, const uint8_t* cb_log2_size, const uint8_t* cb_part_mode,
+                               const uint8_t* tu_split);
 /* the accumulated description (valid until the recorder is modified or freed) */
 const de265hip_picture_desc* de265hip_recorder_desc(de265hip_recorder*);
 int  de265hip_recorder_submit(de265hip_decoder*, int dst_slot, de265hip_recorder*, de265hip_picture** out);
@@ -398,7 +425,8 @@ int  de265hip_pipeline_new(de265hip_pipeline** out, de265hip_decoder*, int n_wor
 int  de265hip_pipeline_submit(de265hip_pipeline*, int dst_slot, de265hip_prepare_fn prepare, void* user,
                               void* const planes[3], const ptrdiff_t stride_bytes[3], uint64_t* ticket);
 /* The same for a host that already holds the picture's description (no prepare step): `desc` and the arrays it points to
- * stay valid and unchanged until the ticket has been waited for (or the pipeline drained). */
+ * stay valid and unchanged until the ticket has been waited for (or the pipeline drained).  Unstructured: the edge bits come in
+ * desc->blk_flags (a host that wants the device to derive them submits a recorder with de265hip_record_structure). */
 int  de265hip_pipeline_submit_desc(de265hip_pipeline*, int dst_slot, const de265hip_picture_desc* desc,
                                    void* const planes[3], const ptrdiff_t stride_bytes[3], uint64_t* ticket);
 int  de265hip_pipeline_wait(de265hip_pipeline*, uint64_t ticket);
@@ -424,6 +452,10 @@ uint64_t de265hip_debug_last_build_hash(void);
  * same plus the CPU rehearsal of the scan's passes.  keep: the last picture, its arena in host memory (de265hip_debug_picture_*,
  * de265hip_picture_free). */
 int  de265hip_debug_build_host_only_ex(const de265hip_picture_desc*, int reps, int mode, de265hip_picture** keep);
+/* The same for a structured build (structure may be NULL: unstructured).  The host runs the device's edge-bit body into the kept
+ * arena; de265hip_debug_picture_layout's out[25] is the offset of blk_flags there, out[26] that of the EdgeJob (-1: none). */
+int  de265hip_debug_build_host_only_structured(const de265hip_picture_desc*, const de265hip_cu_structure*, int reps, int mode,
+                                               de265hip_picture** keep);
 /* Test entry points: fault injection (a run other runs wait for is left out of the pictures built from now on; spin_limit
  * bounds k_run's dependency waits, 0 = default), and read-back of a picture's run-side structures (offsets and counts, then
  * bytes of its arena) for tests/test_scan_equivalence.py. */

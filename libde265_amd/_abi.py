@@ -122,6 +122,13 @@ class PictureDesc(C.Structure):
     ]
 
 
+class CuStructure(C.Structure):
+    """de265hip_cu_structure: the CU / TU structure planes of a structured build (the device derives the edge bits)"""
+    _fields_ = [
+        ("cb_log2_size", C.POINTER(C.c_uint8)), ("cb_part_mode", C.POINTER(C.c_uint8)), ("tu_split", C.POINTER(C.c_uint8)),
+    ]
+
+
 class PictureStats(C.Structure):
     _fields_ = [
         ("n_levels", C.c_int32), ("n_tu_tasks", C.c_int32), ("n_mc_tasks", C.c_int32),

@@ -22,12 +22,13 @@ EXPORTS = [
     "de265hip_dpb_copy", "de265hip_dpb_download_async", "de265hip_dpb_download_planes_async", "de265hip_dpb_wait_copy_out", "de265hip_dpb_wait", "de265hip_host_alloc", "de265hip_host_free",
     "de265hip_pipeline_new", "de265hip_pipeline_submit", "de265hip_pipeline_submit_desc", "de265hip_pipeline_wait", "de265hip_pipeline_drain", "de265hip_pipeline_free",
     "de265hip_debug_build_host_only", "de265hip_debug_last_build_hash", "de265hip_debug_build_host_only_ex",
+    "de265hip_debug_build_host_only_structured",
     "de265hip_debug_fault_injection", "de265hip_debug_picture_layout", "de265hip_debug_picture_read",
-    "de265hip_picture_build", "de265hip_picture_build_host", "de265hip_picture_enqueue", "de265hip_picture_enqueue_batch", "de265hip_picture_ready", "de265hip_picture_run", "de265hip_decoder_sync", "de265hip_picture_free",
+    "de265hip_picture_build", "de265hip_picture_build_host", "de265hip_picture_build_structured", "de265hip_picture_build_host_structured", "de265hip_picture_enqueue", "de265hip_picture_enqueue_batch", "de265hip_picture_ready", "de265hip_picture_run", "de265hip_decoder_sync", "de265hip_picture_free",
     "de265hip_decode_picture", "de265hip_picture_get_stats",
     "de265hip_set_profiling", "de265hip_get_kernel_times", "de265hip_derive_edge_flags", "de265hip_intra_used_units",
     "de265hip_recorder_new", "de265hip_recorder_free", "de265hip_record_tu", "de265hip_record_pu",
-    "de265hip_record_pcm", "de265hip_record_slice", "de265hip_record_ctb", "de265hip_record_blk_planes",
+    "de265hip_record_pcm", "de265hip_record_slice", "de265hip_record_ctb", "de265hip_record_blk_planes", "de265hip_record_structure",
     "de265hip_recorder_desc", "de265hip_recorder_submit",
     "de265hip_fn_transform_add", "de265hip_fn_transform_skip_add", "de265hip_fn_transform_bypass_add",
     "de265hip_fn_put_qpel", "de265hip_fn_put_epel", "de265hip_fn_put_pred",
@@ -88,6 +89,7 @@ def lib():
     L.de265hip_pipeline_free.restype = None
     L.de265hip_debug_build_host_only.argtypes = [pp(_abi.PictureDesc), i32]
     L.de265hip_debug_build_host_only_ex.argtypes = [pp(_abi.PictureDesc), i32, i32, pp(vp)]
+    L.de265hip_debug_build_host_only_structured.argtypes = [pp(_abi.PictureDesc), pp(_abi.CuStructure), i32, i32, pp(vp)]
     L.de265hip_debug_fault_injection.argtypes = [vp, i32, C.c_uint32]
     L.de265hip_debug_picture_layout.argtypes = [vp, pp(C.c_int64)]
     L.de265hip_debug_picture_read.argtypes = [vp, C.c_int64, C.c_int64, vp]
@@ -95,6 +97,8 @@ def lib():
     L.de265hip_debug_last_build_hash.argtypes = []
     L.de265hip_picture_build.argtypes = [vp, i32, pp(_abi.PictureDesc), pp(vp)]
     L.de265hip_picture_build_host.argtypes = [vp, i32, pp(_abi.PictureDesc), pp(vp)]
+    L.de265hip_picture_build_structured.argtypes = [vp, i32, pp(_abi.PictureDesc), pp(_abi.CuStructure), pp(vp)]
+    L.de265hip_picture_build_host_structured.argtypes = [vp, i32, pp(_abi.PictureDesc), pp(_abi.CuStructure), pp(vp)]
     L.de265hip_picture_enqueue.argtypes = [vp]
     L.de265hip_picture_ready.argtypes = [vp]
     L.de265hip_picture_enqueue_batch.argtypes = [pp(vp), i32]
@@ -119,6 +123,7 @@ def lib():
     L.de265hip_record_slice.argtypes = [vp, pp(_abi.SliceParams)]
     L.de265hip_record_ctb.argtypes = [vp, i32, pp(_abi.CtbInfo)]
     L.de265hip_record_blk_planes.argtypes = [vp, vp, vp, vp]
+    L.de265hip_record_structure.argtypes = [vp, vp, vp, vp]
     L.de265hip_recorder_desc.argtypes = [vp]
     L.de265hip_recorder_desc.restype = pp(_abi.PictureDesc)
     L.de265hip_recorder_submit.argtypes = [vp, i32, vp, pp(vp)]
@@ -365,10 +370,16 @@ class Decoder:
         _chk(lib().de265hip_dpb_copy(self._h, slot, other._h, other_slot), "dpb_copy")
 
     # --- pictures ---
-    def build(self, dst_slot, desc):
+    def build(self, dst_slot, desc, structure=None):
+        """structure: (cb_log2_size, cb_part_mode, tu_split) uint8 arrays (extra items are ignored, e.g. the fourth of
+        SynthPicture.structure()): a structured build - the device derives the edge bits and ignores those of blk_flags."""
         dptr = desc if isinstance(desc, C.POINTER(_abi.PictureDesc)) else C.pointer(desc)
         h = C.c_void_p()
-        _chk(lib().de265hip_picture_build(self._h, dst_slot, dptr, C.byref(h)), "picture_build")
+        if structure is None:
+            _chk(lib().de265hip_picture_build(self._h, dst_slot, dptr, C.byref(h)), "picture_build")
+        else:
+            cs, _keep = cu_structure(structure)
+            _chk(lib().de265hip_picture_build_structured(self._h, dst_slot, dptr, C.byref(cs), C.byref(h)), "picture_build_structured")
         return Picture(self, h)
 
     def run(self, pic, last_stage=_abi.STAGE_FINAL):
@@ -434,6 +445,11 @@ class Recorder:
         _chk(L.de265hip_record_blk_planes(self._h, C.cast(d.blk_flags, C.c_void_p), C.cast(d.blk_qp_y, C.c_void_p),
                                           C.cast(d.blk_motion, C.c_void_p)), "record_blk_planes")
 
+    def record_structure(self, cb_log2_size, cb_part_mode, tu_split):
+        """the CU / TU structure planes (copied): submit() and the pipeline then build the picture structured"""
+        planes = [np.ascontiguousarray(a, dtype=np.uint8) for a in (cb_log2_size, cb_part_mode, tu_split)]
+        _chk(lib().de265hip_record_structure(self._h, *[a.ctypes.data for a in planes]), "record_structure")
+
     @property
     def desc(self):
         return lib().de265hip_recorder_desc(self._h)
@@ -453,6 +469,13 @@ class Recorder:
             self.free()
         except Exception:
             pass
+
+
+def cu_structure(structure):
+    """(cb_log2_size, cb_part_mode, tu_split[, ...]) -> (_abi.CuStructure, the contiguous uint8 arrays it points into: keep them)"""
+    planes = [np.ascontiguousarray(a, dtype=np.uint8) for a in list(structure)[:3]]
+    u8 = C.POINTER(C.c_uint8)
+    return _abi.CuStructure(*[C.cast(a.ctypes.data, u8) for a in planes]), planes
 
 
 def derive_edge_flags(params, slices, n_slices, ctbs, cb_log2_size, cb_part_mode, tu_split, blk_flags):

@@ -241,7 +241,8 @@ struct de265hip_picture {
     uint64_t up_sig = 0;                      // upload issued through the HSA runtime: its completion signal (hsa_signal_t::handle)
     uint8_t* host_base = nullptr; size_t upload_bytes = 0; hipEvent_t stage_event = nullptr;
     size_t o_sync = 0, clear_bytes = 0, o_mot = 0, o_pus = 0, o_sl = 0, o_l0 = 0, o_l0x = 0, o_cpos = 0, nblk = 0;
-    bool mot_given = true, check_on_device = false;
+    size_t o_edj = 0;                         // structured: the EdgeJob (edge_core.h)
+    bool mot_given = true, check_on_device = false, structured = false;
     int n_pus = 0, n_slices = 0, n_l0chk = 0, n_l0xchk = 0;
   } enq;
   ScanCounts h_counts_dry;            // (dry decoders: no ring)
@@ -1422,21 +1423,36 @@ void de265hip_picture_free(de265hip_picture* p)
 
 static int finish_scan(de265hip_picture* pic);
 static thread_local bool g_defer_enqueue = false;        // de265hip_picture_build_host: the build stops before its HIP calls
-static int picture_build_impl(de265hip_decoder* dec, int dst_slot, const de265hip_picture_desc* d, de265hip_picture** out);
+static int picture_build_impl(de265hip_decoder* dec, int dst_slot, const de265hip_picture_desc* d, const de265hip_cu_structure* cs,
+                              de265hip_picture** out);
 
-int de265hip_picture_build(de265hip_decoder* dec, int dst_slot, const de265hip_picture_desc* d,
-                           de265hip_picture** out)
+// cs: the CU / TU structure of a structured build (the device derives the edge bits), nullptr for the host's own edge bits
+static int picture_build_any(de265hip_decoder* dec, int dst_slot, const de265hip_picture_desc* d, const de265hip_cu_structure* cs,
+                             de265hip_picture** out)
 {
   if (!dec || !d || !out) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
   // builds in progress are counted: a picture joins `live` only at the end of its build, and until then the geometry guard
   // of another worker's build must still see it (a change of picture size between consecutive submissions)
   { std::lock_guard<std::mutex> lk(dec->mu); dec->building++; }
-  const int rc = picture_build_impl(dec, dst_slot, d, out);
+  const int rc = picture_build_impl(dec, dst_slot, d, cs, out);
   { std::lock_guard<std::mutex> lk(dec->mu); dec->building--; }
   return rc;
 }
 
-static int picture_build_impl(de265hip_decoder* dec, int dst_slot, const de265hip_picture_desc* d, de265hip_picture** out)
+int de265hip_picture_build(de265hip_decoder* dec, int dst_slot, const de265hip_picture_desc* d, de265hip_picture** out)
+{
+  return picture_build_any(dec, dst_slot, d, nullptr, out);
+}
+
+int de265hip_picture_build_structured(de265hip_decoder* dec, int dst_slot, const de265hip_picture_desc* d, const de265hip_cu_structure* cs,
+                                      de265hip_picture** out)
+{
+  if (!cs) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  return picture_build_any(dec, dst_slot, d, cs, out);
+}
+
+static int picture_build_impl(de265hip_decoder* dec, int dst_slot, const de265hip_picture_desc* d, const de265hip_cu_structure* cs,
+                              de265hip_picture** out)
 {
   *out = nullptr;
   const de265hip_pic_params& p = d->params;
@@ -1493,6 +1509,22 @@ static int picture_build_impl(de265hip_decoder* dec, int dst_slot, const de265hi
   if (d->n_ctbs != g.ctbs_w * g.ctbs_h) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
   for (int i = 0; i < d->n_ctbs; i++)
     if (d->ctbs[i].slice_idx >= d->n_slices) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  // structured build: what the device's edge-bit body (edge_core.h) relies on - CB sizes it can look for, part modes it knows.  One
+  // branch-free pass over the two MinCb planes (130 KB at 4K); the rest of the structure is the host's to get right, and wrong
+  // split bits or an untiled quadtree only make the edge bits wrong (the body's reads are bounded by the picture whatever they say)
+  const int mincb = 1 << std::min(std::max(p.log2_min_cb_size, 0), 6);
+  const size_t n_cb = (size_t)((p.width + mincb - 1) / mincb) * ((p.height + mincb - 1) / mincb), n_tb = (size_t)g.tbs_w * g.tbs_h;
+  if (cs) {
+    if (!cs->cb_log2_size || !cs->cb_part_mode || !cs->tu_split || p.log2_min_cb_size < 3 || p.log2_min_cb_size > p.log2_ctb_size)
+      return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+    const uint8_t lo = (uint8_t)p.log2_min_cb_size, hi = (uint8_t)p.log2_ctb_size;
+    uint8_t bad = 0;
+    for (size_t i = 0; i < n_cb; i++) {
+      const uint8_t v = cs->cb_log2_size[i];
+      bad |= (uint8_t)((v != 0) & ((v < lo) | (v > hi))) | (uint8_t)(cs->cb_part_mode[i] > 7);
+    }
+    if (bad) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  }
 
   de265hip_picture* pic = new (std::nothrow) de265hip_picture();
   if (!pic) return DE265HIP_ERROR_OUT_OF_MEMORY;
@@ -1881,7 +1913,7 @@ static int picture_build_impl(de265hip_decoder* dec, int dst_slot, const de265hi
   if (cr_mirror && (mirror_broken || cbq_n != 0)) {         // not the pattern the shortcut relies on: once more, the long way
     delete pic;
     g_no_cr_mirror = true;
-    const int rc2 = picture_build_impl(dec, dst_slot, d, out);
+    const int rc2 = picture_build_impl(dec, dst_slot, d, cs, out);
     g_no_cr_mirror = false;
     return rc2;
   }
@@ -2532,7 +2564,12 @@ static int picture_build_impl(de265hip_decoder* dec, int dst_slot, const de265hi
     uint8_t any = 0;
     const uint8_t* bf = d->blk_flags;
     for (size_t i = 0; i < nblk; i++) any |= bf[i];
-    if (any & 0xF0) pic->any_edges = true;
+    if (cs) {
+      // the bytes carry no edges in a structured build: what derive_edgeFlags returns instead - some CTB lies in a slice with
+      // deblocking enabled (deblock.cc:213-222, :228-237)
+      for (int a = 0; a < d->n_ctbs && !pic->any_edges; a++)
+        if (!d->slices[d->ctbs[a].slice_idx].slice_deblocking_filter_disabled_flag) pic->any_edges = true;
+    } else if (any & 0xF0) pic->any_edges = true;
     P.has_exempt = ((any & DE265HIP_BLK_BYPASS) || ((any & DE265HIP_BLK_PCM) && p.pcm_loop_filter_disable_flag)) ? 1 : 0;
   }
 
@@ -2604,6 +2641,9 @@ static int picture_build_impl(de265hip_decoder* dec, int dst_slot, const de265hi
   const size_t o_mbx = L.add(n_mailboxes ? mbx.size() * 4 : 0), o_mbs = L.add(n_mailboxes ? mb_segs.size() * 4 : 0);
   const size_t o_grp = L.add(dev_scan ? (size_t)d->n_ctbs * 4 : 0), o_rs2ts = L.add(dev_scan ? (size_t)d->n_ctbs * 4 : 0), o_ts2rs = L.add(dev_scan ? (size_t)d->n_ctbs * 4 : 0);
   const size_t o_dorder = L.add(dev_scan ? (size_t)d->n_ctbs * 4 : 0);
+  // a structured build's CU / TU structure and the EdgeJob that points into the arena (nothing for an unstructured one: its arena
+  // and upload stay what they were)
+  const size_t o_cbl = L.add(cs ? n_cb : 0), o_cbp = L.add(cs ? n_cb : 0), o_tsp = L.add(cs ? n_tb : 0), o_edj = L.add(cs ? sizeof(EdgeJob) : 0);
   const size_t upload_bytes = L.total;                 // everything above is written by the host
   // device-only scratch: boundary strengths, residual blocks, run flags (no staging, no upload)
   const size_t o_bs = L.add(nblk);
@@ -2704,6 +2744,18 @@ static int picture_build_impl(de265hip_decoder* dec, int dst_slot, const de265hi
     put(o_rs2ts, g.rs2ts.data(), (size_t)d->n_ctbs * 4); put(o_ts2rs, g.ts2rs.data(), (size_t)d->n_ctbs * 4);
     put(o_dorder, g.diag_order.data(), (size_t)d->n_ctbs * 4);
   }
+  if (cs) {
+    put(o_cbl, cs->cb_log2_size, n_cb); put(o_cbp, cs->cb_part_mode, n_cb); put(o_tsp, cs->tu_split, n_tb);
+    uint8_t* dbase = dec->dry ? host_base : (uint8_t*)pic->arena_buf.ptr;      // (where the arena will be: the pointers of the job)
+    EdgeJob ej; memset(&ej, 0, sizeof(ej));
+    ej.cb_log2 = dbase + o_cbl; ej.cb_part = dbase + o_cbp; ej.tu_split = dbase + o_tsp;
+    ej.ctbs = (const de265hip_ctb_info*)(dbase + o_ctb); ej.slices = (const de265hip_slice_params*)(dbase + o_sl);
+    ej.tile_id = (const uint16_t*)(dbase + o_tile); ej.flags = dbase + o_flags;
+    ej.w4 = g.w4; ej.h4 = g.h4; ej.lc = lc; ej.lmincb = p.log2_min_cb_size; ej.lt = lt;
+    ej.cbs_w = (p.width + mincb - 1) / mincb; ej.tbs_w = g.tbs_w; ej.ctbs_w = g.ctbs_w; ej.lf_across_tiles = p.loop_filter_across_tiles_enabled_flag;
+    memcpy(host.data() + o_edj, &ej, sizeof(ej));
+    if (dec->dry) edge_flags_units(ej, 0, 1);         // (no device: the same body on the host, into the kept arena)
+  }
 
   pt.mark("staging");
   pic->arena = dec->dry ? (void*)host_base : pic->arena_buf.ptr;
@@ -2742,6 +2794,7 @@ static int picture_build_impl(de265hip_decoder* dec, int dst_slot, const de265hi
     E.o_sync = o_sync; E.clear_bytes = clear_bytes; E.o_mot = o_mot; E.o_pus = o_pus; E.o_sl = o_sl; E.o_l0 = o_l0; E.o_l0x = o_l0x; E.o_cpos = o_cpos;
     E.nblk = nblk; E.mot_given = mot_given; E.check_on_device = !dev_scan && !host_checks_positions;
     E.n_pus = d->n_pus; E.n_slices = d->n_slices; E.n_l0chk = (int)l0.size(); E.n_l0xchk = (int)SC.l0_rext.size();
+    E.structured = cs != nullptr; E.o_edj = o_edj;
     pic->cap_resid = cap_resid;
   }
   pic->dev_scan = dev_scan;
@@ -2759,6 +2812,7 @@ static int picture_build_impl(de265hip_decoder* dec, int dst_slot, const de265hi
   pic->d_bs = base + o_bs;
   pic->d_sync = (uint32_t*)(base + o_sync); pic->d_resid = (int16_t*)(base + o_resid);
   pic->d_mb = (unsigned long long*)(base + o_mb);
+  pic->o_layout[13] = (int64_t)o_flags; pic->o_layout[14] = cs ? (int64_t)o_edj : -1;
   if (dev_scan) {
     pic->d_runs = SB.runs; pic->d_deps = SB.deps; pic->d_run_tus = SB.run_tus; pic->d_slots = SB.slots;
     pic->d_l0 = SB.l0; pic->d_l0_rext = SB.l0x; pic->d_mbx = SB.mbx; pic->d_mbsegs = SB.mb_segs; pic->d_front_idx = SB.front_idx;
@@ -2873,6 +2927,7 @@ int de265hip_picture_enqueue_batch(de265hip_picture** pics, int n)
     ScanBatch J; memset(&J, 0, sizeof(J)); J.pad = run2_lane0 ? 1 : 0;      // (pad bit 0: the mailbox readers' pass on one lane, scan_core.h's loop: the parity variant)
     PrepBatch PJ; PJ.n = 0; PJ.pad = 0;
     de265hip_picture* done[SCAN_BATCH]; int n_done = 0;
+    de265hip_picture* own_edges[SCAN_BATCH]; int n_own_edges = 0;      // structured pictures whose edge bits get a launch of their own
     auto tnow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tl = tnow();
     auto sec = [&](int k) { const double t = tnow(); dec->t_sec[k] += t - tl; if (t - tl > dec->t_sec_max[k]) dec->t_sec_max[k] = t - tl; tl = t; };
@@ -2932,12 +2987,18 @@ int de265hip_picture_enqueue_batch(de265hip_picture** pics, int n)
           jb.mo_pus = q.pus; jb.mo_slices = q.slices; jb.mo_plane = q.motion; jb.mo_n_pus = q.n_pus; jb.mo_n_slices = q.n_slices; jb.mo_w4 = q.w4; jb.mo_h4 = q.h4;
           q.n_pus = 0;
         }
+        // the edge bits by the same launch, behind the motion plane's workgroups
+        if (E.structured) {
+          if (own_prep) jb.ed = (const EdgeJob*)(base + E.o_edj);
+          else own_edges[n_own_edges++] = pic;
+        }
         pic->scan_pending = true;
       } else {
         HIPCHK(hipMemsetAsync(dec->d_err_ring + pic->ring_idx, 0, 4, cs), DE265HIP_ERROR_DECODING);
         if (E.check_on_device && E.n_l0chk + E.n_l0xchk > 0)
           hipLaunchKernelGGL(k_check_coeffs, dim3((E.n_l0chk + E.n_l0xchk + 15) / 16), dim3(256), 0, cs, (const TuTask*)(base + E.o_l0), E.n_l0chk,
                              (const TuTask*)(base + E.o_l0x), E.n_l0xchk, (uint16_t*)(base + E.o_cpos), dec->d_err_ring + pic->ring_idx);
+        if (E.structured) own_edges[n_own_edges++] = pic;
       }
       done[n_done++] = pic;
       sec(5);
@@ -2953,6 +3014,8 @@ int de265hip_picture_enqueue_batch(de265hip_picture** pics, int n)
         if (q.n_pus > 0) hipLaunchKernelGGL(k_motion_from_pus, dim3((q.n_pus + 15) / 16), dim3(256), 0, cs, Pm, q.pus, q.n_pus, q.slices, q.n_slices, q.motion);
       }
     }
+    for (int i = 0; i < n_own_edges; i++)
+      HIPCHK(edge_enqueue(cs, (const EdgeJob*)((uint8_t*)own_edges[i]->arena + own_edges[i]->enq.o_edj), own_edges[i]->enq.nblk), DE265HIP_ERROR_DECODING);
     if (J.n) HIPCHK(scan_enqueue_batch(cs, J), DE265HIP_ERROR_DECODING);
     sec(6);
     for (int i = 0; i < n_done; i++) HIPCHK(hipEventRecord(done[i]->uploaded, cs), DE265HIP_ERROR_DECODING);
@@ -2976,7 +3039,17 @@ int de265hip_picture_ready(de265hip_picture* pic)
 int de265hip_picture_build_host(de265hip_decoder* dec, int dst_slot, const de265hip_picture_desc* d, de265hip_picture** out)
 {
   g_defer_enqueue = true;
-  const int rc = de265hip_picture_build(dec, dst_slot, d, out);
+  const int rc = picture_build_any(dec, dst_slot, d, nullptr, out);
+  g_defer_enqueue = false;
+  return rc;
+}
+
+int de265hip_picture_build_host_structured(de265hip_decoder* dec, int dst_slot, const de265hip_picture_desc* d, const de265hip_cu_structure* cs,
+                                           de265hip_picture** out)
+{
+  if (!cs) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  g_defer_enqueue = true;
+  const int rc = picture_build_any(dec, dst_slot, d, cs, out);
   g_defer_enqueue = false;
   return rc;
 }
@@ -2993,6 +3066,13 @@ int de265hip_debug_build_host_only(const de265hip_picture_desc* d, int reps) { r
 // its host-memory arena; de265hip_picture_free).
 int de265hip_debug_build_host_only_ex(const de265hip_picture_desc* d, int reps, int mode, de265hip_picture** keep)
 {
+  return de265hip_debug_build_host_only_structured(d, nullptr, reps, mode, keep);
+}
+
+// cs != nullptr: a structured build; the host runs the edge-bit body into the arena (the tests read it back)
+int de265hip_debug_build_host_only_structured(const de265hip_picture_desc* d, const de265hip_cu_structure* cs, int reps, int mode,
+                                              de265hip_picture** keep)
+{
   if (!d || mode < 0 || mode > 2) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
   if (keep) *keep = nullptr;
   de265hip_decoder* dec = new de265hip_decoder();
@@ -3002,7 +3082,7 @@ int de265hip_debug_build_host_only_ex(const de265hip_picture_desc* d, int reps, 
   int rc = 0;
   for (int i = 0; i < reps && !rc; i++) {
     de265hip_picture* pic = nullptr;
-    rc = de265hip_picture_build(dec, DE265HIP_MAX_DPB_SLOTS - 1, d, &pic);
+    rc = picture_build_any(dec, DE265HIP_MAX_DPB_SLOTS - 1, d, cs, &pic);
     g_last_build_hash = (uint64_t)dec->pooled_bytes;
     if (pic && !rc && mode == 2) rc = pic->scan_rc;
     if (keep && pic && i == reps - 1 && !rc) { pic->dec = nullptr; *keep = pic; }
@@ -3094,6 +3174,7 @@ int de265hip_debug_picture_layout(de265hip_picture* pic, int64_t out[32])
   out[22] = pic->dev_scan ? (int64_t)pic->SP.cap_runs : pic->n_runs;
   out[23] = (int64_t)pic->arena_bytes;
   out[24] = pic->n_workers;
+  out[25] = pic->o_layout[13]; out[26] = pic->o_layout[14];
   return 0;
 }
 
@@ -3101,7 +3182,14 @@ int de265hip_debug_picture_layout(de265hip_picture* pic, int64_t out[32])
 int de265hip_debug_picture_read(de265hip_picture* pic, int64_t offset, int64_t bytes, void* dst)
 {
   if (!pic || !dst || offset < 0 || bytes < 0 || (size_t)(offset + bytes) > pic->arena_bytes) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
-  if (!pic->dry_arena.empty()) { memcpy(dst, pic->dry_arena.data() + offset, (size_t)bytes); return 0; }
+  if (!pic->dry_arena.empty()) {
+    // (a dry build keeps only the part of the arena it wrote - the uploaded part, unless the passes ran on the host too: the
+    //  device-only rest reads as zeros)
+    const size_t have = pic->dry_arena.size(), from = std::min((size_t)offset, have), n = std::min((size_t)bytes, have - from);
+    memcpy(dst, pic->dry_arena.data() + from, n);
+    memset((uint8_t*)dst + n, 0, (size_t)bytes - n);
+    return 0;
+  }
   if (!pic->dec || !pic->arena) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
   if (pic->enq.pending) { const int erc = de265hip_picture_enqueue(pic); if (erc) return erc; }
   if (pic->uploaded) HIPCHK(hipEventSynchronize(pic->uploaded), DE265HIP_ERROR_DECODING);
@@ -3578,6 +3666,8 @@ struct de265hip_recorder {
   std::vector<de265hip_pcm> pcms; std::vector<uint16_t> pcm_samples;
   std::vector<uint8_t> flags; std::vector<int8_t> qp; std::vector<de265hip_motion> motion;
   bool have_motion = false;
+  std::vector<uint8_t> cb_log2, cb_part, tu_split;     // de265hip_record_structure: the picture is built structured
+  bool have_structure = false;
 };
 
 int de265hip_recorder_new(de265hip_recorder** out, const de265hip_pic_params* params, const uint8_t* scaling_factors)
@@ -3675,10 +3765,35 @@ const de265hip_picture_desc* de265hip_recorder_desc(de265hip_recorder* r)
   return &d;
 }
 
-int de265hip_recorder_submit(de265hip_decoder* dec, int dst_slot, de265hip_recorder* r, de265hip_picture** out)
+int de265hip_record_structure(de265hip_recorder* r, const uint8_t* cb_log2_size, const uint8_t* cb_part_mode, const uint8_t* tu_split)
+{
+  if (!r || !cb_log2_size || !cb_part_mode || !tu_split) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  const de265hip_pic_params& p = r->d.params;
+  if (p.log2_min_cb_size < 3 || p.log2_min_cb_size > p.log2_ctb_size || p.log2_min_tb_size < 2 || p.log2_min_tb_size > p.log2_ctb_size)
+    return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  const int mincb = 1 << p.log2_min_cb_size, ctb = 1 << p.log2_ctb_size, dl = p.log2_ctb_size - p.log2_min_tb_size;
+  const size_t n_cb = (size_t)((p.width + mincb - 1) / mincb) * ((p.height + mincb - 1) / mincb);
+  const size_t n_tb = (size_t)(((p.width + ctb - 1) / ctb) << dl) * (((p.height + ctb - 1) / ctb) << dl);
+  r->cb_log2.assign(cb_log2_size, cb_log2_size + n_cb); r->cb_part.assign(cb_part_mode, cb_part_mode + n_cb);
+  r->tu_split.assign(tu_split, tu_split + n_tb);
+  r->have_structure = true;
+  return DE265HIP_OK;
+}
+
+// the host stage of a recorder's picture, structured if the recorder holds a structure (also the pipeline's `prepare` path:
+// pipeline.hip; not part of the ABI)
+__attribute__((visibility("hidden"))) int d265_recorder_build(de265hip_decoder* dec, int dst_slot, de265hip_recorder* r, bool host_only, de265hip_picture** out)
 {
   if (!r) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
-  return de265hip_picture_build(dec, dst_slot, de265hip_recorder_desc(r), out);
+  const de265hip_picture_desc* d = de265hip_recorder_desc(r);
+  if (!r->have_structure) return host_only ? de265hip_picture_build_host(dec, dst_slot, d, out) : de265hip_picture_build(dec, dst_slot, d, out);
+  const de265hip_cu_structure cs{ r->cb_log2.data(), r->cb_part.data(), r->tu_split.data() };
+  return host_only ? de265hip_picture_build_host_structured(dec, dst_slot, d, &cs, out) : de265hip_picture_build_structured(dec, dst_slot, d, &cs, out);
+}
+
+int de265hip_recorder_submit(de265hip_decoder* dec, int dst_slot, de265hip_recorder* r, de265hip_picture** out)
+{
+  return d265_recorder_build(dec, dst_slot, r, false, out);
 }
 
 // ------------------------------------------------------------------ Part B

@@ -225,9 +225,19 @@ void k_scan_tus(ScanBatch J)
 {
   if (blockIdx.y >= (unsigned)J.n) return;
   SCAN_PRIO();
-  if ((int)blockIdx.x >= J.tus_blocks) {                    // the workgroups behind the pass's own: the picture's motion plane
+  if ((int)blockIdx.x >= J.tus_blocks) {                    // the workgroups behind the pass's own: the picture's motion plane, its edge bits
     const ScanJob& Q = J.job[blockIdx.y];
-    if (Q.mo_plane) motion_from_pus_body(Q.mo_pus, Q.mo_n_pus, Q.mo_slices, Q.mo_n_slices, Q.mo_plane, Q.mo_w4, Q.mo_h4, (int)blockIdx.x - J.tus_blocks, (int)gridDim.x - J.tus_blocks);
+    const int wg = (int)blockIdx.x - J.tus_blocks;
+    if (wg < J.mo_blocks) {
+      if (Q.mo_plane) motion_from_pus_body(Q.mo_pus, Q.mo_n_pus, Q.mo_slices, Q.mo_n_slices, Q.mo_plane, Q.mo_w4, Q.mo_h4, wg, J.mo_blocks);
+    } else if (Q.ed) {
+      // The passes of this launch and the next read the INTRA bit of the same plane (scan_core.h scan_tu: rotation, constrained
+      // intra availability).  Each unit's byte is stored once, whole, with the host's low nibble: a reader sees the old or the new
+      // byte, and both carry the same INTRA bit.  No lane reads another lane's byte.
+      const EdgeJob E = *Q.ed;
+      const int ed_wgs = (int)gridDim.x - J.tus_blocks - J.mo_blocks;
+      edge_flags_units(E, (long)(wg - J.mo_blocks) * 256 + threadIdx.x, (long)ed_wgs * 256);
+    }
     return;
   }
   const ScanParams& P = J.job[blockIdx.y].P; const ScanBufs& B = J.job[blockIdx.y].B;
@@ -1322,6 +1332,24 @@ void k_motion_batch(PrepBatch J)
   motion_from_pus_body(Q.pus, Q.n_pus, Q.slices, Q.n_slices, Q.motion, Q.w4, Q.h4, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// the edge bits of one structured picture (edge_core.h) by a launch of their own: the paths without the device-side scan (or
+// without own_prep), like k_motion_from_pus there.  Same body and the same single whole-byte store per unit as k_scan_tus's.
+__global__ __launch_bounds__(256)
+void k_edge_flags(const EdgeJob* __restrict__ ed)
+{
+  SCAN_PRIO();
+  const EdgeJob E = *ed;
+  edge_flags_units(E, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256);
+}
+
+hipError_t edge_enqueue(hipStream_t st, const EdgeJob* ed, size_t n_units)
+{
+  // (a bounded grid that walks the units: see scan_enqueue_batch)
+  const unsigned blocks = (unsigned)std::min<size_t>((n_units + 255) / 256, 1024);
+  if (blocks) hipLaunchKernelGGL(k_edge_flags, dim3(blocks), dim3(256), 0, st, ed);
+  return hipGetLastError();
+}
+
 hipError_t prep_enqueue_batch(hipStream_t st, const PrepBatch& J)
 {
   if (J.n <= 0) return hipSuccess;
@@ -1395,10 +1423,15 @@ hipError_t scan_enqueue_batch(hipStream_t st, const ScanBatch& J)
   // (the per-TU pass's launch also carries the motion planes, behind its own workgroups: ScanJob::mo_*)
   int most_pus = 0;
   for (int i = 0; i < J.n; i++) if (J.job[i].mo_plane) most_pus = std::max(most_pus, J.job[i].mo_n_pus);
+  // (and the edge bits of the structured pictures, behind the motion planes: ScanJob::ed, a lane per 4x4 unit and step)
+  size_t most_units = 0;
+  for (int i = 0; i < J.n; i++) if (J.job[i].ed) most_units = std::max(most_units, (size_t)((J.job[i].P.width + 3) / 4) * ((J.job[i].P.height + 3) / 4));
   ScanBatch K = J;
   K.tus_blocks = max_tus > 0 ? (int)std::min<unsigned>((max_tus + 255) / 256, per_pic) : 0;
   const unsigned mo_blocks = most_pus > 0 ? std::min<unsigned>((most_pus + 15) / 16, std::max(16u, per_pic / 2)) : 0u;
-  if (K.tus_blocks + mo_blocks > 0) hipLaunchKernelGGL(k_scan_tus, dim3((unsigned)K.tus_blocks + mo_blocks, ny), dim3(256), 0, st, K);
+  const unsigned ed_blocks = most_units > 0 ? (unsigned)std::min<size_t>((most_units + 255) / 256, per_pic) : 0u;
+  K.mo_blocks = (int)mo_blocks;
+  if (K.tus_blocks + mo_blocks + ed_blocks > 0) hipLaunchKernelGGL(k_scan_tus, dim3((unsigned)K.tus_blocks + mo_blocks + ed_blocks, ny), dim3(256), 0, st, K);
   if (max_tus > 0) {
     hipLaunchKernelGGL(k_scan_ctbs, dim3(std::min<unsigned>(max_ctbs, per_pic), ny), dim3(64), 0, st, J);
     // (the number of runs is only known on the device: fixed grids of wavefronts walk the run lists)

@@ -9,6 +9,9 @@
 #include "../../include/de265_hip.h"
 #include "env.h"
 
+// host.hip: de265hip_recorder_submit's host stage (structured if the recorder holds a structure)
+extern "C" int d265_recorder_build(de265hip_decoder* dec, int dst_slot, de265hip_recorder* r, bool host_only, de265hip_picture** out);
+
 #include <array>
 #include <chrono>
 #include <condition_variable>
@@ -87,7 +90,7 @@ void worker(de265hip_pipeline* p)
     else {
       rc = j.prepare(j.user, &rec);
       if (!rc && !rec) rc = DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
-      if (!rc) rc = de265hip_picture_build_host(p->dec, j.slot, de265hip_recorder_desc(rec), &pic);
+      if (!rc) rc = d265_recorder_build(p->dec, j.slot, rec, true, &pic);      // (structured if the recorder holds a structure)
       if (rec) de265hip_recorder_free(rec);
     }
     const double t2 = now();

@@ -4,6 +4,7 @@
 #include <cstring>
 #include "kernels.h"
 #include "scan_core.h"
+#include "edge_core.h"
 
 namespace d265 {
 
@@ -28,9 +29,14 @@ struct ScanLayout {
 // for).  A launch of its own - 9 us alone - shows as 90 us in the kernel trace of the product path, like every small kernel of the
 // chain; one launch fewer per batch, but no measurable change of the product's rate (4 250-4 290 against 4 310-4 370 pictures/s with
 // DE265HIP_MOTION_LAUNCH=1, box noise): what those 90 us are is time in the stream's queue, not work.
+// ed: the edge bits of a structured picture (edge_core.h), by more workgroups of the same launch behind the motion plane's (nullptr:
+// the host handed the edge bits over).  One pointer per job into the picture's arena: the batch stays below 4 KB of arguments.
 struct ScanJob { ScanParams P; ScanBufs B; uint32_t cap_resid, cap_levels;
-                 const de265hip_pu* mo_pus; const de265hip_slice_params* mo_slices; de265hip_motion* mo_plane; int mo_n_pus, mo_n_slices, mo_w4, mo_h4, mo_pad; };
-struct ScanBatch { int n; int pad; int tus_blocks; int pad2; ScanJob job[SCAN_BATCH]; };      // tus_blocks: the per-TU pass's workgroups per picture (the rest of its grid: the motion plane)
+                 const de265hip_pu* mo_pus; const de265hip_slice_params* mo_slices; de265hip_motion* mo_plane; const EdgeJob* ed;
+                 int mo_n_pus, mo_n_slices, mo_w4, mo_h4, mo_pad; };
+// tus_blocks: the per-TU pass's workgroups per picture; the rest of its grid: mo_blocks for the motion plane, then the edge bits
+struct ScanBatch { int n; int pad; int tus_blocks; int mo_blocks; ScanJob job[SCAN_BATCH]; };
+static_assert(sizeof(ScanBatch) < 4000, "kernel arguments of k_scan_tus");
 hipError_t scan_enqueue_batch(hipStream_t st, const ScanBatch& J);
 
 // what has to be set before the passes (and the picture's kernels) may run, for the pictures of a batch in ONE launch each:
@@ -46,6 +52,8 @@ struct PrepJob {
 };
 struct PrepBatch { int n; int pad; PrepJob job[SCAN_BATCH]; };
 hipError_t prep_enqueue_batch(hipStream_t st, const PrepBatch& J);
+// the edge bits of ONE structured picture by a launch of their own (the paths without the device-side scan, or without own_prep)
+hipError_t edge_enqueue(hipStream_t st, const EdgeJob* ed, size_t n_units);
 hipError_t scan_enqueue(hipStream_t st, const ScanParams& P, const ScanBufs& B, const ScanLayout& L, uint8_t* base, uint32_t cap_resid);
 void scan_host_run(const ScanParams& P, const ScanBufs& B, const ScanLayout& L, uint8_t* base, uint32_t cap_resid);
 
