@@ -341,6 +341,68 @@ int  de265hip_dpb_plane(de265hip_decoder*, int slot, int c_idx,
  * planes are sent with RCCL on zero-copy tensor views of de265hip_dpb_plane (libde265_amd/farm.py). */
 int  de265hip_dpb_copy(de265hip_decoder* src_dec, int src_slot, de265hip_decoder* dst_dec, int dst_slot);
 
+/* ---- export: a decoded picture into caller-owned DEVICE buffers, cropped and converted by one kernel (k_export).
+ *
+ * Window.  crop_left / _right / _top / _bottom are in luma samples: libde265's spec.crop_* = conf_win_*_offset x SubWidthC /
+ * SubHeightC (image.cc:336-339).  Left / right must be multiples of SubWidthC, top / bottom of SubHeightC (of the slot's
+ * chroma format; monochrome: 1 and 1); the chroma window is the luma window divided by the same factors.  An empty window is
+ * refused.  The window is offset by SAMPLES at every bit depth, as the standard defines it.  (libde265 offsets pixels_confwin by
+ * samples on a byte pointer, image.cc:385-387: the same for 8-bit pictures and for crops at the right and bottom only, a few
+ * samples off for a left or top crop of a picture of more than 8 bits.)
+ *
+ * Layouts.  PLANAR: dst[0..2] receive Y, Cb, Cr (monochrome: dst[0] only).  SEMIPLANAR: dst[0] receives Y and dst[1] Cb,Cr
+ * interleaved per chroma sample, Cb first (NV12 / NV16 / NV24 at 8 bit; P010 / P210 / P410-style with MSB16); refused for
+ * chroma_format_idc 0.
+ *
+ * Sample formats, per component with ITS bit depth bd (bdY, bdC):
+ *   NATIVE  uint8 for bd == 8, uint16 holding the decoded value above: bit-identical to de265hip_dpb_download
+ *   MSB16   uint16 holding v << (16 - bd)
+ *   F32     float (float)v / (float)((1 << bd) - 1), correctly rounded
+ *   F16     the F32 value rounded to nearest-even to IEEE half (what torch.Tensor.half() does)
+ *
+ * Destinations.  pitch_bytes[c]: at least the row's bytes and a multiple of the element size; dst[c] aligned to the element
+ * size.  Destination c holds rows[c] rows of row_bytes[c] bytes each (de265hip_export_geometry): (rows - 1) x pitch + row_bytes
+ * bytes.  Planes the layout does not use (monochrome chroma, SEMIPLANAR's dst[2]) are ignored. */
+#define DE265HIP_EXPORT_PLANAR      0
+#define DE265HIP_EXPORT_SEMIPLANAR  1
+#define DE265HIP_EXPORT_NATIVE      0
+#define DE265HIP_EXPORT_MSB16       1
+#define DE265HIP_EXPORT_F32         2
+#define DE265HIP_EXPORT_F16         3
+#define DE265HIP_EXPORT_AFTER_CONSUMER 0x1u   /* flags: the export also starts behind the work already on consumer_stream */
+#define DE265HIP_EXPORT_NULL_STREAM    0x2u   /* flags: a NULL consumer_stream is the device's null stream (a torch default stream), not none */
+typedef struct de265hip_export_desc {
+  int32_t  layout;                    /* DE265HIP_EXPORT_PLANAR / _SEMIPLANAR */
+  int32_t  format;                    /* DE265HIP_EXPORT_NATIVE / _MSB16 / _F32 / _F16 */
+  int32_t  crop_left, crop_right, crop_top, crop_bottom;      /* luma samples */
+  void*    dst[3];                    /* device memory of the decoder's device */
+  int64_t  pitch_bytes[3];
+  uint32_t flags;                     /* DE265HIP_EXPORT_AFTER_CONSUMER | DE265HIP_EXPORT_NULL_STREAM */
+  uint32_t reserved;                  /* 0 */
+} de265hip_export_desc;              /* 80 bytes on every LP64 target */
+/* Validates an export descriptor against a picture geometry and reports what each destination must hold: rows[c] rows of
+ * row_bytes[c] bytes (0 and 0 for a plane the layout does not use).  A pure host function (no HIP call, no decoder).  Layout,
+ * format, flags and window are checked first and the sizes written as soon as they pass; then the destinations: wanted planes
+ * need a non-NULL dst and a valid pitch - except when every dst is NULL, the allocator's query, which returns 0 with the sizes.
+ * 0 or DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE; rows / row_bytes may be NULL. */
+int  de265hip_export_geometry(int width, int height, int bit_depth_luma, int bit_depth_chroma, int chroma_format_idc,
+                              const de265hip_export_desc* desc, int64_t rows[3], int64_t row_bytes[3]);
+/* Enqueue the export of the picture a DPB slot holds; never waits on the host.  The kernel runs on the stream that wrote the
+ * slot (the decoder's, or the writer lane's; behind a de265hip_dpb_copy into the slot), so it comes behind the picture and
+ * takes no hardware queue of its own.  The slot's next writer waits for it on the device: a picture run into the slot, an
+ * upload, a fill, a copy into it, a re-allocation, de265hip_decoder_free.  A non-NULL consumer_stream (a hipStream_t of the
+ * decoder's device) waits for the export on the device; with DE265HIP_EXPORT_AFTER_CONSUMER the export also starts only after
+ * the work already enqueued on consumer_stream (a ring of destinations the consumer may still be reading; the decoder's
+ * stream then waits for the consumer too).  export_id (may be NULL): 1, 2, .. per slot since its allocation.
+ * DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE, with nothing enqueued, for an unallocated slot, a descriptor
+ * de265hip_export_geometry refuses for the slot's picture, every dst NULL, or AFTER_CONSUMER without a consumer stream (NULL
+ * without DE265HIP_EXPORT_NULL_STREAM). */
+int  de265hip_dpb_export_async(de265hip_decoder*, int slot, const de265hip_export_desc* desc, void* consumer_stream,
+                               uint64_t* export_id);
+/* Wait on the host for export `export_id` of the slot; reports a failed picture like de265hip_dpb_wait_copy_out.  A number from
+ * before the slot's last re-allocation is not an error: that export finished when the slot was re-allocated. */
+int  de265hip_dpb_wait_export(de265hip_decoder*, int slot, uint64_t export_id);
+
 /* Build: host-side preprocessing (intra availability + dependency levels,
  * level sort, MC task split) into a pinned staging buffer and ASYNCHRONOUS upload of the command
  * buffers on the decoder's copy stream into a pooled device arena (no allocation and no host-side wait
@@ -432,6 +494,18 @@ int  de265hip_pipeline_submit_desc(de265hip_pipeline*, int dst_slot, const de265
 int  de265hip_pipeline_wait(de265hip_pipeline*, uint64_t ticket);
 int  de265hip_pipeline_drain(de265hip_pipeline*);          /* every submitted picture launched, finished and copied out */
 void de265hip_pipeline_free(de265hip_pipeline*);           /* drains first */
+/* The same as de265hip_pipeline_submit / _submit_desc, with the picture exported (de265hip_dpb_export_async, no consumer stream;
+ * the descriptor is copied, AFTER_CONSUMER and NULL_STREAM are refused) right after its launch instead of a copy-out.  The destinations stay
+ * the caller's and must stay valid until the ticket has been waited for or the pipeline drained.  de265hip_pipeline_wait(ticket)
+ * covers the export; an export the slot's picture refuses is that ticket's error. */
+int  de265hip_pipeline_submit_export(de265hip_pipeline*, int dst_slot, de265hip_prepare_fn prepare, void* user,
+                                     const de265hip_export_desc* export_desc, uint64_t* ticket);
+int  de265hip_pipeline_submit_desc_export(de265hip_pipeline*, int dst_slot, const de265hip_picture_desc* desc,
+                                          const de265hip_export_desc* export_desc, uint64_t* ticket);
+/* Blocks only until the ticket's picture has been LAUNCHED (with its export), then makes consumer_stream wait for the export on
+ * the device (NULL: the device's null stream).  The ticket's error if it failed (it is reported again by de265hip_pipeline_wait); PARAMETER_OUT_OF_RANGE for a
+ * ticket without an export; 0 without any wait for a ticket that has been waited for already. */
+int  de265hip_pipeline_export_to_stream(de265hip_pipeline*, uint64_t ticket, void* consumer_stream);
 
 /* de265hip_picture_build in two steps, for a host that wants every HIP call of a decoder issued by ONE of its threads (the
  * pipeline does: many threads calling into the HIP runtime for one device queue up behind its locks).  _build_host: the host

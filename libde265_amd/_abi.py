@@ -139,3 +139,19 @@ class PictureStats(C.Structure):
         ("alg_bytes_sao", C.c_int64),
         ("alg_bytes_intra_front", C.c_int64), ("n_front_runs", C.c_int32), ("pad", C.c_int32),
     ]
+
+
+# de265hip_export_desc (de265hip_dpb_export_async): layouts, sample formats, flags
+EXPORT_PLANAR, EXPORT_SEMIPLANAR = 0, 1
+EXPORT_NATIVE, EXPORT_MSB16, EXPORT_F32, EXPORT_F16 = 0, 1, 2, 3
+EXPORT_AFTER_CONSUMER = 0x1
+EXPORT_NULL_STREAM = 0x2
+
+
+class ExportDesc(C.Structure):
+    _fields_ = [
+        ("layout", C.c_int32), ("format", C.c_int32),
+        ("crop_left", C.c_int32), ("crop_right", C.c_int32), ("crop_top", C.c_int32), ("crop_bottom", C.c_int32),
+        ("dst", C.c_void_p * 3), ("pitch_bytes", C.c_int64 * 3),
+        ("flags", C.c_uint32), ("reserved", C.c_uint32),
+    ]

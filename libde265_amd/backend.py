@@ -19,7 +19,9 @@ EXPORTS = [
     "de265hip_version", "de265hip_device_count",
     "de265hip_decoder_new", "de265hip_decoder_free", "de265hip_decoder_set_lanes",
     "de265hip_dpb_alloc", "de265hip_dpb_alloc_ex", "de265hip_dpb_chroma_format", "de265hip_dpb_upload", "de265hip_dpb_fill", "de265hip_dpb_download", "de265hip_dpb_plane", "de265hip_dpb_info",
-    "de265hip_dpb_copy", "de265hip_dpb_download_async", "de265hip_dpb_download_planes_async", "de265hip_dpb_wait_copy_out", "de265hip_dpb_wait", "de265hip_host_alloc", "de265hip_host_free",
+    "de265hip_dpb_copy", "de265hip_dpb_download_async",
+    "de265hip_export_geometry", "de265hip_dpb_export_async", "de265hip_dpb_wait_export",
+    "de265hip_pipeline_submit_export", "de265hip_pipeline_submit_desc_export", "de265hip_pipeline_export_to_stream", "de265hip_dpb_download_planes_async", "de265hip_dpb_wait_copy_out", "de265hip_dpb_wait", "de265hip_host_alloc", "de265hip_host_free",
     "de265hip_pipeline_new", "de265hip_pipeline_submit", "de265hip_pipeline_submit_desc", "de265hip_pipeline_wait", "de265hip_pipeline_drain", "de265hip_pipeline_free",
     "de265hip_debug_build_host_only", "de265hip_debug_last_build_hash", "de265hip_debug_build_host_only_ex",
     "de265hip_debug_build_host_only_structured",
@@ -84,6 +86,12 @@ def lib():
     L.de265hip_pipeline_submit.argtypes = [vp, i32, PREPARE_FN, vp, pp(vp), pp(C.c_ssize_t), pp(C.c_uint64)]
     L.de265hip_pipeline_submit_desc.argtypes = [vp, i32, C.POINTER(_abi.PictureDesc), pp(vp), pp(C.c_ssize_t), pp(C.c_uint64)]
     L.de265hip_pipeline_wait.argtypes = [vp, C.c_uint64]
+    L.de265hip_export_geometry.argtypes = [i32, i32, i32, i32, i32, pp(_abi.ExportDesc), pp(C.c_int64), pp(C.c_int64)]
+    L.de265hip_dpb_export_async.argtypes = [vp, i32, pp(_abi.ExportDesc), vp, pp(C.c_uint64)]
+    L.de265hip_dpb_wait_export.argtypes = [vp, i32, C.c_uint64]
+    L.de265hip_pipeline_submit_export.argtypes = [vp, i32, PREPARE_FN, vp, pp(_abi.ExportDesc), pp(C.c_uint64)]
+    L.de265hip_pipeline_submit_desc_export.argtypes = [vp, i32, C.POINTER(_abi.PictureDesc), pp(_abi.ExportDesc), pp(C.c_uint64)]
+    L.de265hip_pipeline_export_to_stream.argtypes = [vp, C.c_uint64, vp]
     L.de265hip_pipeline_drain.argtypes = [vp]
     L.de265hip_pipeline_free.argtypes = [vp]
     L.de265hip_pipeline_free.restype = None
@@ -175,11 +183,12 @@ class Pipeline:
     launched in submission order; submit(slot, make_recorder, planes) -> ticket, wait(ticket)."""
 
     def __init__(self, dec, n_workers=2):
-        self._dec, self._h, self._keep = dec, C.c_void_p(), {}
+        self._dec, self._h, self._keep, self._exports = dec, C.c_void_p(), {}, {}
         _chk(lib().de265hip_pipeline_new(C.byref(self._h), dec._h, n_workers), "pipeline_new")
 
-    def submit(self, slot, make_recorder, pinned=None):
-        """make_recorder() -> backend.Recorder, called on a pipeline worker thread; pinned: _PinnedPlanes or None"""
+    def submit(self, slot, make_recorder, pinned=None, export=None):
+        """make_recorder() -> backend.Recorder, called on a pipeline worker thread; pinned: _PinnedPlanes or None;
+        export: an ExportSpec (export_spec()) - the picture is exported into its tensors instead of copied out"""
         def cb(user, out):
             try:
                 rec = make_recorder()
@@ -194,33 +203,137 @@ class Pipeline:
         planes = (C.c_void_p * 3)(*(pinned.ptrs if pinned else [None] * 3))
         strides = (C.c_ssize_t * 3)(*(pinned.strides if pinned else [0] * 3))
         t = C.c_uint64()
-        _chk(lib().de265hip_pipeline_submit(self._h, slot, fn, None, planes, strides, C.byref(t)), "pipeline_submit")
+        if export is not None:
+            if pinned is not None:
+                raise ValueError("pipeline submit: a picture is either exported or copied out")
+            _chk(lib().de265hip_pipeline_submit_export(self._h, slot, fn, None, C.byref(export.desc), C.byref(t)), "pipeline_submit_export")
+            self._exports[t.value] = export
+        else:
+            _chk(lib().de265hip_pipeline_submit(self._h, slot, fn, None, planes, strides, C.byref(t)), "pipeline_submit")
         self._keep[t.value] = (fn, planes, strides)   # the callback object must outlive the call on the worker thread
         return t.value
 
-    def submit_desc(self, slot, desc, pinned=None):
-        """a ready-made description (POINTER(PictureDesc), kept alive by the caller until the ticket is waited for)"""
+    def submit_desc(self, slot, desc, pinned=None, export=None):
+        """a ready-made description (POINTER(PictureDesc), kept alive by the caller until the ticket is waited for);
+        export: an ExportSpec, as for submit()"""
         planes = (C.c_void_p * 3)(*(pinned.ptrs if pinned else [None] * 3))
         strides = (C.c_ssize_t * 3)(*(pinned.strides if pinned else [0] * 3))
         t = C.c_uint64()
         dptr = desc if isinstance(desc, C.POINTER(_abi.PictureDesc)) else C.pointer(desc)
-        _chk(lib().de265hip_pipeline_submit_desc(self._h, slot, dptr, planes, strides, C.byref(t)), "pipeline_submit_desc")
+        if export is not None:
+            if pinned is not None:
+                raise ValueError("pipeline submit_desc: a picture is either exported or copied out")
+            _chk(lib().de265hip_pipeline_submit_desc_export(self._h, slot, dptr, C.byref(export.desc), C.byref(t)), "pipeline_submit_desc_export")
+            self._exports[t.value] = export
+        else:
+            _chk(lib().de265hip_pipeline_submit_desc(self._h, slot, dptr, planes, strides, C.byref(t)), "pipeline_submit_desc")
         self._keep[t.value] = (dptr, planes, strides)
         return t.value
 
     def wait(self, ticket):
         _chk(lib().de265hip_pipeline_wait(self._h, ticket), "pipeline_wait")
         self._keep.pop(ticket, None)
+        self._exports.pop(ticket, None)
+
+    def export_to_stream(self, ticket, stream=None):
+        """the tensors of a ticket submitted with export=: blocks until the picture has been launched, then makes `stream` (default
+        torch.cuda.current_stream()) wait for the export on the device.  The tensors stay the pipeline's to write until the
+        ticket has been waited for.  Before the same tensors go to another submit, what `stream` reads from them must have
+        finished too (the next export does not wait for it): synchronise `stream`, or wait on an event recorded behind the read.
+        The tensors are marked as used on `stream` (record_stream), so that freeing them waits for its reads."""
+        import torch          # (import torch before the first libde265_hip.so call in such a process: tests/conftest.py)
+        spec = self._exports[ticket]
+        st = stream if stream is not None else torch.cuda.current_stream(spec.tensors[0].device)
+        _chk(lib().de265hip_pipeline_export_to_stream(self._h, ticket, C.c_void_p(st.cuda_stream)), "pipeline_export_to_stream")
+        for t in spec.tensors:
+            t.record_stream(st)
+        return list(spec.tensors)
 
     def drain(self):
         _chk(lib().de265hip_pipeline_drain(self._h), "pipeline_drain")
         self._keep.clear()
+        self._exports.clear()
 
     def close(self):
         if self._h:
             lib().de265hip_pipeline_free(self._h)
             self._h = C.c_void_p()
             self._keep.clear()
+            self._exports.clear()
+
+
+EXPORT_LAYOUTS = {"planar": _abi.EXPORT_PLANAR, "semiplanar": _abi.EXPORT_SEMIPLANAR}
+EXPORT_FORMATS = {"native": _abi.EXPORT_NATIVE, "msb16": _abi.EXPORT_MSB16, "f32": _abi.EXPORT_F32, "f16": _abi.EXPORT_F16}
+
+
+def export_geometry(width, height, bit_depth_luma, bit_depth_chroma, chroma_format, desc):
+    """de265hip_export_geometry: (rc, rows[3], row_bytes[3]) of an _abi.ExportDesc for a picture geometry (no GPU needed)"""
+    rows, rb = (C.c_int64 * 3)(), (C.c_int64 * 3)()
+    rc = lib().de265hip_export_geometry(width, height, bit_depth_luma, bit_depth_chroma, chroma_format, C.byref(desc), rows, rb)
+    return rc, list(rows), list(rb)
+
+
+class ExportSpec:
+    """the destination of an export: the C descriptor and the torch tensors it points into.  Planar: [Y (h, w), Cb (ch, cw),
+    Cr (ch, cw)] (monochrome: [Y]); semi-planar: [Y (h, w), CbCr (ch, cw, 2)].  dtype: "native" (uint8 at 8 bit, uint16
+    above), "msb16" (uint16), "f32" (float32), "f16" (float16), each component with its own bit depth.  crop: (left, right,
+    top, bottom) in luma samples.  out: tensors of those shapes and dtypes on `device` (rows may be padded: any row pitch the C
+    call accepts, the samples of a row contiguous) or None: allocated on `device`, on `stream` (default: the current stream).
+
+    Allocation: torch's caching allocator hands out a block that work still queued on the allocating stream may be using (it
+    assumes the block's next user runs on that stream), while the export writes from the decoder's stream.  So when it allocates,
+    the constructor waits on the host until the allocating stream's queued work has finished - except for Decoder.export, which
+    orders the export behind that stream on the device instead (AFTER_CONSUMER on the stream it allocates on: `_ordered`)."""
+
+    def __init__(self, width, height, bit_depth_luma, bit_depth_chroma, chroma_format, layout="planar", dtype="native",
+                 crop=(0, 0, 0, 0), out=None, device=None, after_consumer=False, stream=None, _ordered=False):
+        import torch          # (import torch before the first libde265_hip.so call in such a process: tests/conftest.py)
+        device = torch.device(device if device is not None else "cuda")
+        if device.type != "cuda":
+            raise ValueError("export: device %s is not a GPU" % device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if layout not in EXPORT_LAYOUTS or dtype not in EXPORT_FORMATS:
+            raise ValueError("export: layout %r / dtype %r unknown" % (layout, dtype))
+        d = _abi.ExportDesc()
+        d.layout, d.format = EXPORT_LAYOUTS[layout], EXPORT_FORMATS[dtype]
+        d.crop_left, d.crop_right, d.crop_top, d.crop_bottom = [int(v) for v in crop]
+        d.flags = _abi.EXPORT_AFTER_CONSUMER if after_consumer else 0
+        rc, rows, rb = export_geometry(width, height, bit_depth_luma, bit_depth_chroma, chroma_format, d)
+        _chk(rc, "export_geometry")
+        bds = [bit_depth_luma, bit_depth_chroma, bit_depth_chroma]
+        tdt = {"msb16": torch.uint16, "f32": torch.float32, "f16": torch.float16}
+        shapes, dts = [], []
+        for c in range(3):
+            if not rows[c]:
+                continue
+            dt = tdt.get(dtype) or (torch.uint8 if bds[c] <= 8 else torch.uint16)
+            n = rb[c] // dt.itemsize
+            shapes.append((rows[c], n) if not (c == 1 and layout == "semiplanar") else (rows[c], n // 2, 2))
+            dts.append(dt)
+        if out is None:
+            st = stream if stream is not None else torch.cuda.current_stream(device)
+            with torch.cuda.stream(st):
+                out = [torch.empty(sh, dtype=dt, device=device) for sh, dt in zip(shapes, dts)]
+            if not _ordered:
+                st.synchronize()            # (the blocks' earlier users on `st` are done: nothing orders the export behind them)
+        out = list(out)
+        if len(out) != len(shapes):
+            raise ValueError("export: %d output tensors, the layout has %d planes" % (len(out), len(shapes)))
+        for c, (t, sh, dt) in enumerate(zip(out, shapes, dts)):
+            if tuple(t.shape) != sh or t.dtype != dt or t.device != device:
+                raise ValueError("export: plane %d is %s %s on %s, wants %s %s on %s" % (c, tuple(t.shape), t.dtype, t.device, sh, dt, device))
+            inner = (1,) if len(sh) == 2 else (2, 1)
+            if tuple(t.stride())[1:] != inner or t.stride(0) < 1:
+                raise ValueError("export: plane %d must have contiguous rows (strides %s)" % (c, tuple(t.stride())))
+            d.dst[c] = t.data_ptr()
+            d.pitch_bytes[c] = t.stride(0) * dt.itemsize
+        _chk(export_geometry(width, height, bit_depth_luma, bit_depth_chroma, chroma_format, d)[0], "export_geometry")
+        self.desc, self.tensors = d, out
+
+
+class ExportedPlanes(list):
+    """Decoder.export(): the output tensors, with .slot and .export_id (Decoder.wait_export)"""
 
 
 class PinnedPlanes:
@@ -277,6 +390,7 @@ class Decoder:
         h = C.c_void_p()
         _chk(lib().de265hip_decoder_new(C.byref(h), device), "decoder_new")
         self._h = h
+        self._device = device
 
     def close(self):
         if self._h:
@@ -364,6 +478,43 @@ class Decoder:
         p, s = C.c_void_p(), C.c_ssize_t()
         _chk(lib().de265hip_dpb_plane(self._h, slot, c_idx, C.byref(p), C.byref(s)), "dpb_plane")
         return p.value, s.value
+
+    def export_spec(self, slot, layout="planar", dtype="native", crop=(0, 0, 0, 0), out=None, after_consumer=False, stream=None,
+                    _ordered=False):
+        """an ExportSpec for the picture the slot holds now (its geometry), with tensors on the decoder's device"""
+        import torch
+        if self._device < 0:
+            self._device = torch.cuda.current_device()          # (device=-1: the current device, the one the decoder took when made)
+        w, h, by, bc = self.dpb_info(slot)
+        return ExportSpec(w, h, by, bc, lib().de265hip_dpb_chroma_format(self._h, slot), layout, dtype, crop, out,
+                          torch.device("cuda", self._device), after_consumer, stream, _ordered)
+
+    def export(self, slot, layout="planar", dtype="native", crop=(0, 0, 0, 0), out=None, stream=None, after_consumer=False):
+        """de265hip_dpb_export_async: the slot's picture into torch tensors on the decoder's device (ExportSpec: shapes, dtypes,
+        crop), by a kernel behind the picture on the decoder's stream.  `stream` (default torch.cuda.current_stream()) waits for it
+        on the device - no host wait, no sync(); after_consumer: the export also starts only after the work already on `stream`
+        (a ring of `out` tensors the consumer may still be reading).  Returns ExportedPlanes (a list of the tensors).
+        With out=None the tensors are allocated on `stream` and the export always waits for the work already queued there: the
+        allocator may hand out a block that work still reads (the next picture of a consumer loop lands in the block of a picture
+        the consumer has dropped but not finished reading).  The decoder's stream then waits for that work too; with `out` rings
+        and after_consumer only where a ring entry comes round, it does not."""
+        import torch
+        if self._device < 0:
+            self._device = torch.cuda.current_device()
+        dev = torch.device("cuda", self._device)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        spec = self.export_spec(slot, layout, dtype, crop, out, after_consumer or out is None, st, _ordered=True)
+        if not st.cuda_stream:
+            spec.desc.flags |= _abi.EXPORT_NULL_STREAM      # (torch's default stream is the device's null stream)
+        eid = C.c_uint64()
+        _chk(lib().de265hip_dpb_export_async(self._h, slot, C.byref(spec.desc), C.c_void_p(st.cuda_stream), C.byref(eid)), "dpb_export_async")
+        res = ExportedPlanes(spec.tensors)
+        res.slot, res.export_id = slot, eid.value
+        return res
+
+    def wait_export(self, slot, export_id):
+        """de265hip_dpb_wait_export: blocks the host until that export has finished"""
+        _chk(lib().de265hip_dpb_wait_export(self._h, slot, export_id), "dpb_wait_export")
 
     def copy_slot_to(self, slot, other, other_slot):
         """Device-to-device hand-over of a finished reference picture to another decoder."""

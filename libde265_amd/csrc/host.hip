@@ -26,6 +26,7 @@
 #include "kernels.h"
 #include "env.h"
 #include "scan.h"
+#include "export.h"
 
 using namespace d265;
 
@@ -69,6 +70,16 @@ struct Slot {
   uint64_t written_seq = 0;                        // launch number of the writing picture (lane choice)
   hipEvent_t read_done[4] = { nullptr, nullptr, nullptr, nullptr };
   bool rd_valid[4] = { false, false, false, false };
+  // de265hip_dpb_export_async: each export is recorded behind its kernel on the stream that wrote the slot (ex_stream, the
+  // latest's); every writer of the slot - a picture, an upload, a fill, a copy, a re-allocation - waits for ex_done, which
+  // covers the earlier exports of the same content (one stream, or the later export waited for the earlier).  ex_seq counts them.
+  static constexpr int kExRing = 4;
+  hipEvent_t ex_done = nullptr;                    // (= the event of the latest export, one of ex_ev)
+  hipStream_t ex_stream = nullptr;
+  uint64_t ex_seq = 0;
+  hipEvent_t ex_ev[kExRing] = {};
+  uint64_t ex_ev_seq[kExRing] = {};
+  int ex_ev_err_idx[kExRing] = { -1, -1, -1, -1 }; uint64_t ex_ev_err_seq[kExRing] = {};
 };
 constexpr int kMaxLanes = 4;
 constexpr int kForeignWriter = -2;
@@ -109,6 +120,8 @@ struct de265hip_decoder {
   hipStream_t out_stream = nullptr;   // de265hip_dpb_download_async: decoded pictures leave on their own stream, behind an event of `stream`
   bool out_pooled = false;            // ... one of the process's two (DeviceStreams)
   hipEvent_t out_fence = nullptr;
+  hipEvent_t ex_fence = nullptr;      // de265hip_dpb_export_async with DE265HIP_EXPORT_AFTER_CONSUMER: "what the consumer stream has queued"
+  int n_cus = 0;                      // compute units of the device (the export kernel's grid)
   // deferred copy-outs: jobs for the output thread (guarded by g_out_mu), the events their pictures are waited for by
   struct OutJobRec { Slot* s; uint64_t id; int ring; hipEvent_t picture_done; void* dst[3]; const void* src[3]; size_t dpitch[3], spitch[3], row_bytes[3], rows[3]; };
   std::deque<OutJobRec> out_jobs;
@@ -282,6 +295,9 @@ int free_slot(Slot& s)
   if (s.written) { (void)hipEventDestroy(s.written); s.written = nullptr; }
   for (int l = 0; l < kMaxLanes; l++) { if (s.read_done[l]) { (void)hipEventDestroy(s.read_done[l]); s.read_done[l] = nullptr; } s.rd_valid[l] = false; }
   s.writer_lane = -1; s.written_seq = 0;
+  if (s.ex_done) (void)hipEventSynchronize(s.ex_done);   // (an export still reading the planes)
+  for (int r = 0; r < Slot::kExRing; r++) { if (s.ex_ev[r]) (void)hipEventDestroy(s.ex_ev[r]); s.ex_ev[r] = nullptr; s.ex_ev_seq[r] = 0; s.ex_ev_err_idx[r] = -1; }
+  s.ex_done = nullptr; s.ex_stream = nullptr; s.ex_seq = 0;
   if (s.pl[0].ptr) (void)hipFree(s.pl[0].ptr);            // (one allocation: the chroma planes follow the luma plane)
   for (int c = 0; c < 3; c++) s.pl[c].ptr = nullptr;
   s.valid = false;
@@ -928,6 +944,7 @@ void de265hip_decoder_free(de265hip_decoder* d)
   (void)sync_all_lanes(d);
   if (d->out_stream) { (void)hipStreamSynchronize(d->out_stream); if (!d->out_pooled) (void)hipStreamDestroy(d->out_stream); }
   if (d->out_fence) (void)hipEventDestroy(d->out_fence);
+  if (d->ex_fence) (void)hipEventDestroy(d->ex_fence);
   {
     std::lock_guard<std::mutex> lk(d->mu);
     for (de265hip_picture* p : d->live) {
@@ -995,6 +1012,7 @@ int de265hip_dpb_upload(de265hip_decoder* d, int slot, int c, const void* src, p
   if (w == 0 || h == 0) return DE265HIP_OK;               // (a chroma plane of a monochrome picture)
   out_settle(*s);
   if (s->dl_done && s->dl_waited != s->dl_seq) HIPCHK(hipEventSynchronize(s->dl_done), DE265HIP_ERROR_DECODING);
+  if (s->ex_done) HIPCHK(hipEventSynchronize(s->ex_done), DE265HIP_ERROR_DECODING);
   HIPCHK(sync_all_lanes(d), DE265HIP_ERROR_DECODING);
   { std::lock_guard<std::mutex> lk(d->mu); slot_settled(*s); }
   HIPCHK(hipMemcpy2D(s->pl[c].ptr, s->pl[c].stride * bpp, src, (size_t)stride_bytes, w * bpp, h, hipMemcpyHostToDevice),
@@ -1017,6 +1035,7 @@ int de265hip_dpb_fill(de265hip_decoder* d, int slot, int y, int cb, int cr)
     if (c == 0) {
       out_settle(*s);
       if (s->dl_done && s->dl_waited != s->dl_seq) HIPCHK(hipEventSynchronize(s->dl_done), DE265HIP_ERROR_DECODING);
+      if (s->ex_done) HIPCHK(hipEventSynchronize(s->ex_done), DE265HIP_ERROR_DECODING);
       HIPCHK(sync_all_lanes(d), DE265HIP_ERROR_DECODING);
       std::lock_guard<std::mutex> lk(d->mu); slot_settled(*s);
     }
@@ -1370,6 +1389,7 @@ int de265hip_dpb_copy(de265hip_decoder* sd, int ss, de265hip_decoder* dd, int ds
     std::lock_guard<std::mutex> lk(dd->mu);
     out_settle(D);
     if (!rc && D.dl_done && D.dl_waited != D.dl_seq && hipStreamWaitEvent(sd->stream, D.dl_done, 0) != hipSuccess) rc = DE265HIP_ERROR_DECODING;
+    if (!rc && D.ex_done && D.ex_stream != sd->stream && hipStreamWaitEvent(sd->stream, D.ex_done, 0) != hipSuccess) rc = DE265HIP_ERROR_DECODING;
   }
   for (int c = 0; c < 3 && !rc; c++) {
     const int h = c ? S.ch() : S.h;
@@ -1398,6 +1418,147 @@ int de265hip_dpb_copy(de265hip_decoder* sd, int ss, de265hip_decoder* dd, int ds
     if (!rc) S2.rd_valid[0] = true;
   }
   return rc;
+}
+
+// ---- export (include/de265_hip.h, "export"; kernel: k_export.hip)
+static int export_elem_bytes(int format, int bd) { return format == DE265HIP_EXPORT_NATIVE ? (bd > 8 ? 2 : 1) : format == DE265HIP_EXPORT_F32 ? 4 : 2; }
+
+int de265hip_export_geometry(int w, int h, int bdY, int bdC, int cf, const de265hip_export_desc* e, int64_t rows[3], int64_t row_bytes[3])
+{
+  int64_t R[3] = { 0, 0, 0 }, B[3] = { 0, 0, 0 };
+  if (rows) for (int c = 0; c < 3; c++) rows[c] = 0;
+  if (row_bytes) for (int c = 0; c < 3; c++) row_bytes[c] = 0;
+  if (!e || w <= 0 || h <= 0 || bdY < 8 || bdY > 16 || bdC < 8 || bdC > 16 || cf < 0 || cf > 3) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  if ((e->layout != DE265HIP_EXPORT_PLANAR && e->layout != DE265HIP_EXPORT_SEMIPLANAR) || e->format < DE265HIP_EXPORT_NATIVE ||
+      e->format > DE265HIP_EXPORT_F16 || (e->flags & ~(DE265HIP_EXPORT_AFTER_CONSUMER | DE265HIP_EXPORT_NULL_STREAM)))
+    return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  if (e->layout == DE265HIP_EXPORT_SEMIPLANAR && cf == 0) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  const int sw = (cf == 1 || cf == 2) ? 2 : 1, sh = cf == 1 ? 2 : 1;          // SubWidthC / SubHeightC (table 6-1; monochrome 1, 1)
+  if (w % sw || h % sh) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  if (e->crop_left < 0 || e->crop_right < 0 || e->crop_top < 0 || e->crop_bottom < 0 ||
+      e->crop_left % sw || e->crop_right % sw || e->crop_top % sh || e->crop_bottom % sh)
+    return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  const int64_t ow = (int64_t)w - e->crop_left - e->crop_right, oh = (int64_t)h - e->crop_top - e->crop_bottom;
+  if (ow <= 0 || oh <= 0) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;           // (an empty window)
+  const int eY = export_elem_bytes(e->format, bdY), eC = export_elem_bytes(e->format, bdC);
+  R[0] = oh; B[0] = ow * eY;
+  if (cf) {
+    const int64_t cw = ow / sw, ch = oh / sh;
+    if (e->layout == DE265HIP_EXPORT_PLANAR) { R[1] = R[2] = ch; B[1] = B[2] = cw * eC; }
+    else { R[1] = ch; B[1] = 2 * cw * eC; }
+  }
+  if (rows) for (int c = 0; c < 3; c++) rows[c] = R[c];
+  if (row_bytes) for (int c = 0; c < 3; c++) row_bytes[c] = B[c];
+  bool any = false;
+  for (int c = 0; c < 3; c++) if (R[c] && e->dst[c]) any = true;
+  if (!any) return 0;                                    // (every wanted dst NULL: the allocator's query)
+  for (int c = 0; c < 3; c++) {
+    if (!R[c]) continue;
+    const int el = c ? eC : eY;
+    if (!e->dst[c] || e->pitch_bytes[c] < B[c] || e->pitch_bytes[c] % el) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  }
+  return 0;
+}
+
+int de265hip_dpb_export_async(de265hip_decoder* d, int slot, const de265hip_export_desc* e, void* consumer_stream, uint64_t* export_id)
+{
+  if (export_id) *export_id = 0;
+  if (!d || d->dry || !e || slot < 0 || slot >= DE265HIP_MAX_DPB_SLOTS) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  const bool has_consumer = consumer_stream || (e->flags & DE265HIP_EXPORT_NULL_STREAM);      // (NULL_STREAM: NULL is the null stream)
+  if ((e->flags & DE265HIP_EXPORT_AFTER_CONSUMER) && !has_consumer) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  hipStream_t consumer = static_cast<hipStream_t>(consumer_stream);
+  std::lock_guard<std::mutex> lk(d->mu);              // (run_picture swaps the slot's planes under this lock: the pointers read here
+  Slot& s = d->slots[slot];                           //  are those of the picture the launch order has put there)
+  if (!s.valid) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  int64_t rows[3], rb[3];
+  if (const int rc = de265hip_export_geometry(s.w, s.h, s.bdY, s.bdC, s.cf, e, rows, rb)) return rc;
+  ExportJob J; memset(&J, 0, sizeof(J));
+  J.src16 = s.bdY > 8; J.format = e->format;
+  const int sw = (s.cf == 1 || s.cf == 2) ? 2 : 1, sh = s.cf == 1 ? 2 : 1;
+  for (int c = 0; c < 3; c++) {
+    if (!rows[c]) continue;
+    const int el = export_elem_bytes(e->format, c ? s.bdC : s.bdY);
+    if (!e->dst[c] || ((uintptr_t)e->dst[c] % el)) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;     // (every dst NULL, or misaligned)
+    if (rows[c] > 0x7FFFFFFF || rb[c] / el > 0x7FFFFFFF) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+    ExportPlane& P = J.p[J.n_planes];
+    const size_t spx = px_bytes(c ? s.bdC : s.bdY);
+    const int x0 = c ? e->crop_left / sw : e->crop_left, y0 = c ? e->crop_top / sh : e->crop_top;     // (samples, at every bit depth)
+    P.spitch = (int64_t)s.pl[c].stride * spx;
+    const bool semi = c == 1 && e->layout == DE265HIP_EXPORT_SEMIPLANAR;
+    for (int k = 0; k < (semi ? 2 : 1); k++)
+      P.src[k] = static_cast<const uint8_t*>(s.pl[c + k].ptr) + (int64_t)y0 * P.spitch + (int64_t)x0 * spx;
+    P.dst = static_cast<uint8_t*>(e->dst[c]); P.dpitch = e->pitch_bytes[c];
+    P.rows = (int32_t)rows[c]; P.cols = (int32_t)(rb[c] / el); P.bd = c ? s.bdC : s.bdY; P.semi = semi;
+    P.row_start = J.total_rows;
+    J.total_rows += P.rows; J.n_planes++;
+  }
+  // the stream that wrote the slot: the export follows the picture in stream order and needs no queue of its own
+  hipStream_t ws = d->stream;
+  if (d->n_lanes > 1) {
+    if (s.writer_lane >= 0) ws = lane_st(d, s.writer_lane);
+    else if (s.writer_lane == kForeignWriter && s.written) HIPCHK(hipStreamWaitEvent(ws, s.written, 0), DE265HIP_ERROR_DECODING);
+  }
+  if (s.ex_done && s.ex_stream != ws) HIPCHK(hipStreamWaitEvent(ws, s.ex_done, 0), DE265HIP_ERROR_DECODING);     // (ex_done covers them all)
+  if (e->flags & DE265HIP_EXPORT_AFTER_CONSUMER) {
+    if (!d->ex_fence) HIPCHK(hipEventCreateWithFlags(&d->ex_fence, hipEventDisableTiming), DE265HIP_ERROR_OUT_OF_MEMORY);
+    HIPCHK(hipEventRecord(d->ex_fence, consumer), DE265HIP_ERROR_DECODING);
+    HIPCHK(hipStreamWaitEvent(ws, d->ex_fence, 0), DE265HIP_ERROR_DECODING);
+  }
+  if (!d->n_cus) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d->device) != hipSuccess || n <= 0) n = 256;
+    d->n_cus = n;
+  }
+  // the grid is the device's (eight 256-thread workgroups per CU: 32 KiB of 16-byte loads in flight per CU), never more than rows
+  const int grid = std::max(1, std::min(J.total_rows, 8 * d->n_cus));
+  const int r = (int)(s.ex_seq % Slot::kExRing);
+  if (!s.ex_ev[r]) HIPCHK(hipEventCreateWithFlags(&s.ex_ev[r], hipEventDisableTiming), DE265HIP_ERROR_OUT_OF_MEMORY);
+  const hipError_t le = launch_export(J, ws, grid);
+  // (recorded whatever the launch said: the slot's next writer must not wait for an event that never comes)
+  HIPCHK(hipEventRecord(s.ex_ev[r], ws), DE265HIP_ERROR_DECODING);
+  s.ex_done = s.ex_ev[r]; s.ex_stream = ws;
+  s.ex_seq++;
+  s.ex_ev_seq[r] = s.ex_seq; s.ex_ev_err_idx[r] = s.err_idx; s.ex_ev_err_seq[r] = s.err_seq;
+  if (le != hipSuccess) { fprintf(stderr, "de265hip: k_export launch failed: %s\n", hipGetErrorString(le)); return DE265HIP_ERROR_DECODING; }
+  if (has_consumer) HIPCHK(hipStreamWaitEvent(consumer, s.ex_ev[r], 0), DE265HIP_ERROR_DECODING);
+  if (export_id) *export_id = s.ex_seq;
+  return 0;
+}
+
+// the event of export `id` of the slot (or of a later one on the same stream, which covers it), its picture's error-ring entry;
+// false: the export is from before the slot's re-allocation (it has finished)
+static bool export_event(de265hip_decoder* d, int slot, uint64_t id, hipEvent_t* ev, int* eidx)
+{
+  Slot& s = d->slots[slot];
+  *ev = nullptr; *eidx = -1;
+  if (id > s.ex_seq) return false;
+  const int r = (int)((id - 1) % Slot::kExRing);
+  *ev = s.ex_ev[r];
+  if (s.ex_ev_seq[r] == id && s.ex_ev_err_idx[r] >= 0 && d->ring_owner[s.ex_ev_err_idx[r]] == s.ex_ev_err_seq[r]) *eidx = s.ex_ev_err_idx[r];
+  return *ev != nullptr;
+}
+
+int de265hip_dpb_wait_export(de265hip_decoder* d, int slot, uint64_t export_id)
+{
+  if (!d || slot < 0 || slot >= DE265HIP_MAX_DPB_SLOTS || !d->slots[slot].valid || export_id == 0) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  hipEvent_t ev; int eidx;
+  { std::lock_guard<std::mutex> lk(d->mu); if (!export_event(d, slot, export_id, &ev, &eidx)) return 0; }
+  HIPCHK(hipEventSynchronize(ev), DE265HIP_ERROR_DECODING);        // outside the lock: another thread may be enqueueing the next picture
+  uint32_t err = 0;
+  if (eidx >= 0) HIPCHK(hipMemcpy(&err, d->d_err_ring + eidx, 4, hipMemcpyDeviceToHost), DE265HIP_ERROR_DECODING);
+  { std::lock_guard<std::mutex> lo(g_out_mu); if (d->out_failed) err = 1; }
+  return err ? DE265HIP_ERROR_DECODING : 0;
+}
+
+// pipeline.hip (de265hip_pipeline_export_to_stream): `stream` waits on the device for export `id` of the slot (internal: not exported)
+__attribute__((visibility("hidden"))) int d265_export_to_stream(de265hip_decoder* d, int slot, uint64_t id, void* stream)
+{
+  if (!d || slot < 0 || slot >= DE265HIP_MAX_DPB_SLOTS || id == 0) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  std::lock_guard<std::mutex> lk(d->mu);
+  hipEvent_t ev; int eidx;
+  if (!d->slots[slot].valid || !export_event(d, slot, id, &ev, &eidx)) return 0;
+  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(stream), ev, 0), DE265HIP_ERROR_DECODING);
+  return 0;
 }
 
 void de265hip_picture_free(de265hip_picture* p)
@@ -3263,6 +3424,8 @@ int run_picture(de265hip_decoder* dec, de265hip_picture* pic, int last_stage)
   // (a deferred one has to be handed to the runtime first: on the host, until the slot's previous picture is done)
   out_settle(dst);
   if (dst.dl_done && dst.dl_waited != dst.dl_seq && hipStreamWaitEvent(st, dst.dl_done, 0) != hipSuccess) return DE265HIP_ERROR_DECODING;
+  // ... and so must the exports of it (de265hip_dpb_export_async; on this stream they simply precede the picture)
+  if (dst.ex_done && dst.ex_stream != st && hipStreamWaitEvent(st, dst.ex_done, 0) != hipSuccess) return DE265HIP_ERROR_DECODING;
   if (!((pic->upload_waited >> lane) & 1u)) {            // the command buffers arrive on the copy stream
     if (hipStreamWaitEvent(st, pic->uploaded, 0) != hipSuccess) return DE265HIP_ERROR_DECODING;
     pic->upload_waited |= 1u << lane;

@@ -11,6 +11,8 @@
 
 // host.hip: de265hip_recorder_submit's host stage (structured if the recorder holds a structure)
 extern "C" int d265_recorder_build(de265hip_decoder* dec, int dst_slot, de265hip_recorder* r, bool host_only, de265hip_picture** out);
+// host.hip: `stream` waits on the device for export `id` of a slot (de265hip_pipeline_export_to_stream)
+extern "C" int d265_export_to_stream(de265hip_decoder* d, int slot, uint64_t id, void* stream);
 
 #include <array>
 #include <chrono>
@@ -34,8 +36,12 @@ struct PipeJob {
   const de265hip_picture_desc* desc = nullptr;  // de265hip_pipeline_submit_desc: a ready-made description instead of prepare()
   void* plane[3] = { nullptr, nullptr, nullptr };
   ptrdiff_t stride[3] = { 0, 0, 0 };
+  bool exp = false;                             // de265hip_pipeline_submit_export / _desc_export: exported after the launch
+  de265hip_export_desc ex = {};
   double t_sub = 0;
 };
+
+struct Launched { int slot; uint64_t copy_out_id, export_id; };   // (0: none)
 
 }  // namespace
 
@@ -48,7 +54,7 @@ struct de265hip_pipeline {
   std::condition_variable cv;                   // submit / wait / drain
   std::condition_variable cv_launch;            // the launcher: a picture has been built
   std::deque<PipeJob> q;                        // submitted, not yet taken by a worker
-  std::map<uint64_t, std::pair<int, uint64_t>> slot_of;   // launched, copy-out possibly still in flight: ticket -> slot, number of its copy-out (0: none)
+  std::map<uint64_t, Launched> slot_of;         // launched, copy-out / export possibly still in flight: ticket -> slot, their numbers
   std::map<uint64_t, int> failed;               // ticket -> error of prepare / build / run
   struct Built { PipeJob job; de265hip_picture* pic; int rc; bool enqueued; double t_sub, t_b0, t_b1, t_enq, t_ready; };
   std::vector<std::array<double, 4>> chain_trace;   // DE265HIP_PIPE_TRACE: per scan chain: enqueued, reported, pictures built / in flight then
@@ -178,15 +184,16 @@ void launcher(de265hip_pipeline* p)
     }
     if (have_launch) {
       int r = todo.rc;
-      uint64_t copy_out_id = 0;
+      uint64_t copy_out_id = 0, export_id = 0;
       static const bool no_run = d265_env("DE265HIP_PIPE_NO_RUN") != nullptr;      // (experiment: builds, uploads and scans only)
       if (!r && !no_run) r = de265hip_picture_run(p->dec, todo.pic, DE265HIP_STAGE_FINAL);
       if (!r && (todo.job.plane[0] || todo.job.plane[1] || todo.job.plane[2]))
         r = de265hip_dpb_download_planes_async(p->dec, todo.job.slot, todo.job.plane, todo.job.stride, &copy_out_id);
+      if (!r && !no_run && todo.job.exp) r = de265hip_dpb_export_async(p->dec, todo.job.slot, &todo.job.ex, nullptr, &export_id);
       if (todo.pic) de265hip_picture_free(todo.pic);          // never waits (de265_hip.h LIFETIME)
       {
         std::lock_guard<std::mutex> lk(p->mu);
-        if (r) p->failed[todo.job.ticket] = r; else p->slot_of[todo.job.ticket] = { todo.job.slot, copy_out_id };
+        if (r) p->failed[todo.job.ticket] = r; else p->slot_of[todo.job.ticket] = Launched{ todo.job.slot, copy_out_id, export_id };
         p->next_launch++; p->in_flight--;
         if (p->timing) { p->t_lidle += t1 - t0; p->t_launch += now() - t1; }
         if (p->tracing) p->trace.push_back({ (double)todo.job.ticket, todo.t_sub, todo.t_b0, todo.t_b1, todo.t_enq, t1, now(), todo.t_ready });
@@ -218,11 +225,12 @@ int de265hip_pipeline_new(de265hip_pipeline** out, de265hip_decoder* dec, int n_
 }
 
 static int pipeline_submit_job(de265hip_pipeline* p, int dst_slot, de265hip_prepare_fn prepare, void* user, const de265hip_picture_desc* desc,
-                               void* const planes[3], const ptrdiff_t stride_bytes[3], uint64_t* ticket)
+                               void* const planes[3], const ptrdiff_t stride_bytes[3], uint64_t* ticket, const de265hip_export_desc* ex = nullptr)
 {
   if (!p || (!prepare && !desc) || dst_slot < 0 || dst_slot >= DE265HIP_MAX_DPB_SLOTS) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
   PipeJob j;
   j.slot = dst_slot; j.prepare = prepare; j.user = user; j.desc = desc;
+  if (ex) { j.exp = true; j.ex = *ex; }
   for (int c = 0; c < 3; c++) { j.plane[c] = planes ? planes[c] : nullptr; j.stride[c] = (planes && stride_bytes) ? stride_bytes[c] : 0; }
   {
     std::unique_lock<std::mutex> lk(p->mu);
@@ -254,10 +262,42 @@ int de265hip_pipeline_submit_desc(de265hip_pipeline* p, int dst_slot, const de26
   return pipeline_submit_job(p, dst_slot, nullptr, nullptr, desc, planes, stride_bytes, ticket);
 }
 
+int de265hip_pipeline_submit_export(de265hip_pipeline* p, int dst_slot, de265hip_prepare_fn prepare, void* user,
+                                    const de265hip_export_desc* ex, uint64_t* ticket)
+{
+  if (!prepare || !ex || (ex->flags & (DE265HIP_EXPORT_AFTER_CONSUMER | DE265HIP_EXPORT_NULL_STREAM))) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  return pipeline_submit_job(p, dst_slot, prepare, user, nullptr, nullptr, nullptr, ticket, ex);
+}
+
+int de265hip_pipeline_submit_desc_export(de265hip_pipeline* p, int dst_slot, const de265hip_picture_desc* desc,
+                                         const de265hip_export_desc* ex, uint64_t* ticket)
+{
+  if (!desc || !ex || (ex->flags & (DE265HIP_EXPORT_AFTER_CONSUMER | DE265HIP_EXPORT_NULL_STREAM))) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  return pipeline_submit_job(p, dst_slot, nullptr, nullptr, desc, nullptr, nullptr, ticket, ex);
+}
+
+int de265hip_pipeline_export_to_stream(de265hip_pipeline* p, uint64_t ticket, void* consumer_stream)
+{
+  if (!p) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  Launched so;
+  {
+    std::unique_lock<std::mutex> lk(p->mu);
+    if (ticket >= p->next_ticket) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+    p->cv.wait(lk, [&] { return p->next_launch > ticket; });             // launched (or failed): no wait for the device
+    auto f = p->failed.find(ticket);
+    if (f != p->failed.end()) return f->second;                           // (left for pipeline_wait to report as well)
+    auto s = p->slot_of.find(ticket);
+    if (s == p->slot_of.end()) return 0;                                  // waited for before: the export has finished
+    so = s->second;
+  }
+  if (!so.export_id) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
+  return d265_export_to_stream(p->dec, so.slot, so.export_id, consumer_stream);
+}
+
 int de265hip_pipeline_wait(de265hip_pipeline* p, uint64_t ticket)
 {
   if (!p) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
-  std::pair<int, uint64_t> so;
+  Launched so;
   {
     std::unique_lock<std::mutex> lk(p->mu);
     if (ticket >= p->next_ticket) return DE265HIP_ERROR_PARAMETER_OUT_OF_RANGE;
@@ -271,7 +311,9 @@ int de265hip_pipeline_wait(de265hip_pipeline* p, uint64_t ticket)
   }
   // outside the lock: the workers go on launching.  THIS picture's copy-out, not the slot's latest: the slot may have been
   // decoded into and copied out again since (an output queue deeper than the DPB's cycle)
-  return so.second ? de265hip_dpb_wait_copy_out(p->dec, so.first, so.second) : de265hip_dpb_wait(p->dec, so.first);
+  int rc = so.copy_out_id ? de265hip_dpb_wait_copy_out(p->dec, so.slot, so.copy_out_id) : de265hip_dpb_wait(p->dec, so.slot);
+  if (so.export_id) { const int r2 = de265hip_dpb_wait_export(p->dec, so.slot, so.export_id); if (!rc) rc = r2; }
+  return rc;
 }
 
 int de265hip_pipeline_drain(de265hip_pipeline* p)
@@ -285,7 +327,7 @@ int de265hip_pipeline_drain(de265hip_pipeline* p)
   std::vector<int> slots;
   {
     std::lock_guard<std::mutex> lk(p->mu);
-    for (auto& kv : p->slot_of) slots.push_back(kv.second.first);
+    for (auto& kv : p->slot_of) slots.push_back(kv.second.slot);
     p->slot_of.clear();
     if (!rc && !p->failed.empty()) rc = p->failed.begin()->second;
     p->failed.clear();

@@ -98,7 +98,8 @@ def plane_rows(dec, slot):
 def dpb_plane_tensors(dec, slot):
     """Zero-copy torch uint8 views (pitch x rows, padding included) of the planes of a decoder's DPB slot
     (de265hip_dpb_plane); empty planes (monochrome chroma) are left out.  The caller orders access: dec.sync() before
-    another stream reads them, and torch.cuda.synchronize() (or an event) before the decoder's kernels read what torch wrote."""
+    another stream reads them, and torch.cuda.synchronize() (or an event) before the decoder's kernels read what torch wrote.
+    (A consumer of decoded pictures on the same GPU takes them with Decoder.export instead: ordered on the device, no sync.)"""
     import torch          # (import torch before the first libde265_hip.so call in such a process: tests/conftest.py)
     views = []
     for c, rows in enumerate(plane_rows(dec, slot)):
